@@ -13,7 +13,14 @@ the item table replicated) with one RCCL all-reduce on the item-embedding gradie
 per-GPU batch is fixed ("weak" scaling, default; `--scaling strong` fixes the global batch) and
 `value` is the whole-job triplets/s.  The batch never exceeds one epoch of train rows.
 
-Rank 0 prints ONE JSON line (contract in the task statement) that also carries
+Rank 0 prints ONE JSON line: metric, value (triplets/s), unit, higher_is_better, dtype, ms_per_step (the wall time of
+one timed step), the run's shape under "config".  A plain run does only that: set-up, --warmup steps, --steps timed
+steps, the line.  `--dump-outputs DIR` then also writes what the last timed step returned to its caller
+(DIR/user_embedding.npy, DIR/item_embedding.npy: the updated tables, rank 0's rows at N > 1; DIR/loss.npy: the
+step's mean BPR loss), float32, from seeded inputs that are the same in every run with the same arguments.
+
+`--full` adds everything else the benchmark measures (each on further runs of the same step, after the timed ones);
+the line then also carries
   "roofline":     the step's algorithmic bytes (1,560 B per triplet) over the summed average
                   durations of its launches vs the 8 TB/s HBM peak, every launch between its own pair of
                   HIP events inside the timed region; "kernels" / "dominant_kernel" = the per-launch split,
@@ -22,7 +29,10 @@ Rank 0 prints ONE JSON line (contract in the task statement) that also carries
                   "batch_sweep" = the same at 32 / 4,096 / 65,536 / 262,144 / one epoch;
   "host_resident_batches": the PCIe-inclusive rate (batches start in pinned host memory; never `value`);
   "cpu_baseline": the reference's CPU op sequence (oracle/mf_torch_cpu.py) timed on this
-                  host on a bounded sample of the same workload (rank 0, N = 1 only).
+                  host on a bounded sample of the same workload (rank 0, N = 1 only);
+  N > 1:          "collective", "weak" / "strong" (both scaling modes, the exposed collective time, a single-GPU
+                  reference of the strong batch).
+With --full the timed steps also carry the roofline's HIP events (EVENT_EVERY).
 """
 import argparse
 import json
@@ -51,16 +61,34 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=DEFAULT_BATCH, help="triplets per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, batch sweep, host-fed rate, CPU baseline and (N > 1) collective figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (float32 .npy files) into DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-baseline work")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the batch-size sweep (N=1 only; < 1 s of GPU time)")
+    ap.add_argument("--no-sweep", action="store_true",
+                    help="--full without the batch-size sweep and the host-fed rate (N=1 only; < 1 s of GPU time)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1: weak = --batch triplets per GPU; strong = --batch triplets in all (each rank keeps "
                          "the triplets of the users it owns)")
     ap.add_argument("--workload", default="bpr", choices=["bpr", "eval", "ngcf", "cdae"],
                     help="bpr (default, the BASELINE metric) or one of the other full-size paths (N=1 only): "
                          "eval = fused scoring + mask + top-10 + metrics, ngcf = configs[3] step, cdae = configs[4] step")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload != "bpr":
+        ap.error("--dump-outputs: the bpr workload only")
+    return args
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one float32 .npy per array (the tables of the step: 8 + 10 MB at Yelp2018 shape, D = 64)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 def other_workload(args):
@@ -348,7 +376,7 @@ def main():
     U = U_full[shard.lo:shard.hi].contiguous()
     I = (torch.rand(num_items, DIM, generator=g2, device=dev) * 2 - 1) * bi
     step = BPRMFStep(U, I, lr=1e-4, optimizer="adam", world_size=world,
-                     process_group=(dist.group.WORLD if dist else None), time_kernels=True)
+                     process_group=(dist.group.WORLD if dist else None), time_kernels=args.full)
 
     def barrier():
         torch.cuda.synchronize()
@@ -379,13 +407,15 @@ def main():
             el = float(tmax.item())
         return el
 
-    elapsed = measure(step, pool, global_batch, args.steps, args.warmup, timed=True)
-    kt_primary = step.kernel_times()                 # {name: (avg_us, launches, algorithmic bytes per launch)}
+    elapsed = measure(step, pool, global_batch, args.steps, args.warmup, timed=args.full)
     impl_primary, launches_primary = step.impl, step.launches
+    if args.dump_outputs and rank == 0:
+        # before anything else steps these tables (--full's further measurements)
+        dump_outputs(args.dump_outputs, {"user_embedding": step.U, "item_embedding": step.I, "loss": step.loss})
 
     # ---- N > 1: the other scaling mode, the exposed collective time, a single-GPU reference of the strong batch ----
     extra = {}
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as tdist
         k2, w2 = max(5, min(args.steps, 20)), max(2, min(args.warmup, 5))
         secs = {primary: elapsed / args.steps}
@@ -421,11 +451,42 @@ def main():
         del single
     step.check()
     value = global_batch * args.steps / elapsed
+    local_B = sum(t[0].numel() for t in pool) / len(pool)
+    out = {
+        "metric": "BPR triplets/sec @ dim64", "value": round(value, 1), "unit": "triplets/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BPR-MF dim=64 train step (gather+score+loss+grad+dense Adam), "
+                               "synthetic Yelp2018 shape, user-sharded" if world > 1 else
+                               "BPR-MF dim=64 train step (gather+score+loss+grad+dense Adam), synthetic Yelp2018 shape",
+                   "users": num_users, "items": num_items, "interactions": nnz,
+                   "train_triplets_per_epoch": n_train_global, "batch_per_gpu": int(local_B) if strong else B,
+                   "global_batch": global_batch,
+                   # weak scaling keeps the per-GPU batch fixed, so at N > 1 a step spans more than one epoch of
+                   # this (fixed-size) data set: every rank's stream wraps over its shard's rows
+                   "global_batch_in_epochs": round(global_batch / n_train_global, 2),
+                   "optimizer": "adam(dense)", "parallelism": f"user-shard x{world}" if world > 1 else "single",
+                   "step_impl": impl_primary, "data_gen_s": round(data_s, 1)},
+    }
+    if args.full:
+        out["roofline"] = roofline_fields(step, B, local_B, elapsed / args.steps, impl_primary, launches_primary,
+                                          num_users, num_items, world)
+        out.update(extra)
+        if rank == 0 and world == 1:
+            full_single_gpu(args, out, step, pool, n_pool, B, n_train_global, num_users, num_items, dev)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist:
+        dist.destroy_process_group()
+
+
+def roofline_fields(step, B, local_B, sec_per_step, impl_primary, launches_primary, num_users, num_items, world):
+    """--full: the roofline of the timed steps from their HIP events (one pair per launch)"""
+    kt = step.kernel_times()                         # {name: (avg_us, launches, algorithmic bytes per launch)}
     per_triplet = algorithmic_bytes_per_triplet(DIM)
     adam_bytes = 6 * 4 * (num_users + num_items) * DIM          # read p,m,v + write p,m,v on every row (fused)
-
-    # ---- roofline (HIP events inside the timed region, one pair per launch) ----------------------
-    kt = kt_primary
     # single-GPU pull form: recorded steps alternate between one event pair around the whole launch group
     # ("bpr_pull_step": the step's GPU time with its two launch gaps) and one pair per launch (the split)
     group = kt.pop("bpr_pull_step", None) if "owner_pass_item" in kt else None
@@ -437,7 +498,6 @@ def main():
     # the event records themselves and is reported apart ("group_span_us")
     group_us = sum(v[0] for v in kt.values())
     group_span_us = group[0] if group else None
-    local_B = sum(t[0].numel() for t in pool) / len(pool)
     # HBM-side traffic per step from rocprofv3 PMC passes of this same command (FETCH_SIZE doubled
     # as MI355X_MICROARCH.md prescribes, + WRITE_SIZE), committed under profiles/ by
     # scripts/pmc_traffic.py; null when no such measurement is in the tree.
@@ -485,30 +545,15 @@ def main():
                          "algorithmic_bytes": int(local_B * per_triplet),
                          "frac": round(local_B * per_triplet / (group_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
                          "algorithmic_GBps_with_adam_bytes": round((local_B * per_triplet + adam_bytes) / (group_us * 1e-6) / 1e9, 1),
-                         "frac_wall": round(local_B * per_triplet / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}}
+                         "frac_wall": round(local_B * per_triplet / sec_per_step / 1e9 / HBM_PEAK_GBS, 4)}}
+    return roofline
 
-    out = {
-        "metric": "BPR triplets/sec @ dim64", "value": round(value, 1), "unit": "triplets/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BPR-MF dim=64 train step (gather+score+loss+grad+dense Adam), "
-                               "synthetic Yelp2018 shape, user-sharded" if world > 1 else
-                               "BPR-MF dim=64 train step (gather+score+loss+grad+dense Adam), synthetic Yelp2018 shape",
-                   "users": num_users, "items": num_items, "interactions": nnz,
-                   "train_triplets_per_epoch": n_train_global, "batch_per_gpu": int(local_B) if strong else B,
-                   "global_batch": global_batch,
-                   # weak scaling keeps the per-GPU batch fixed, so at N > 1 a step spans more than one epoch of
-                   # this (fixed-size) data set: every rank's stream wraps over its shard's rows
-                   "global_batch_in_epochs": round(global_batch / n_train_global, 2),
-                   "optimizer": "adam(dense)", "parallelism": f"user-shard x{world}" if world > 1 else "single",
-                   "step_impl": impl_primary, "data_gen_s": round(data_s, 1)},
-        "roofline": roofline,
-    }
-    out.update(extra)
 
-    if rank == 0 and world == 1 and not args.no_sweep:
+def full_single_gpu(args, out, step, pool, n_pool, B, n_train_global, num_users, num_items, dev):
+    """--full, N = 1: the batch sweep, the host-fed rate and the CPU baseline, into `out`"""
+    per_triplet = algorithmic_bytes_per_triplet(DIM)
+    adam_bytes = 6 * 4 * (num_users + num_items) * DIM          # read p,m,v + write p,m,v on every row (fused)
+    if not args.no_sweep:
         # the step at the batch sizes training runs use (reference default 32 ... one epoch per step)
         sweep = {}
         for b in (32, 4096, 65536, 262144, n_train_global):
@@ -564,7 +609,7 @@ def main():
             "copy_under_previous_step": {"us_per_step": round(overlapped * 1e6, 1),
                                          "triplets_per_s": round(B / overlapped, 1)}}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if not args.no_cpu_baseline:
         from oracle.mf_torch_cpu import time_steps      # CPU baseline leg only (never the product path)
         cpu_b = B
         cpu_batches = [tuple(t[:cpu_b].cpu() for t in pool[k]) for k in range(min(2, n_pool))]
@@ -581,10 +626,6 @@ def main():
                 tps_b, st_b, sec_b = time_steps(num_users, num_items, DIM, cb, budget_s=3.0)
                 cs[str(b)] = {"triplets_per_s": round(tps_b, 1), "steps": st_b, "seconds": round(sec_b, 1)}
             out["cpu_baseline"]["batch_sweep"] = cs
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

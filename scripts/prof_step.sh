@@ -1,11 +1,12 @@
 #!/bin/bash
-# usage: scripts/prof_step.sh <tag>   (run on the GPU box through gpurun; writes gpurun_out/prof_<tag>)
+# usage: scripts/prof_step.sh <tag>   (GPU box; writes $OUT_DIR/prof_<tag>, OUT_DIR defaults to prof_out)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$1 -- python bench.py --steps 30 --warmup 5 --no-cpu-baseline > gpurun_out/bench_$1.log 2>&1
-grep -o '"value": [0-9.]*, \|"ms_per_step": [0-9.]*' gpurun_out/bench_$1.log | tr '\n' ' '; echo
+out=${OUT_DIR:-prof_out}; mkdir -p $out
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$1 -- python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline > $out/bench_$1.log 2>&1
+grep -o '"value": [0-9.]*, \|"ms_per_step": [0-9.]*' $out/bench_$1.log | tr '\n' ' '; echo
 python - <<PY
 import csv,glob
-f=glob.glob('gpurun_out/prof_$1/*/*_kernel_stats.csv')[0]
+f=glob.glob('$out/prof_$1/*/*_kernel_stats.csv')[0]
 tot=0
 for r in csv.reader(open(f)):
     if 'yr::' in r[0]:

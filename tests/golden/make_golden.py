@@ -23,6 +23,7 @@ backward, Adam) is the reference's own code.
 
 Usage:  python tests/golden/make_golden.py            (writes tests/golden/*.npz, ~1 min)
         python tests/golden/make_golden.py mf_full    (the headline-size MF run, ~20 min -> mf_full.npz)
+        python tests/golden/make_golden.py mf_port    (mf_small's first epoch with an IEEE square root -> mf_port.npz)
 """
 from __future__ import annotations
 
@@ -270,6 +271,33 @@ def golden_mf(out_path, num_users=1000, num_items=1000, mean_items=30.0, embed=3
     )
     print(f"[mf] U={pipe.num_users} I={pipe.num_items} train={len(train_data)} valid={len(valid_data)} "
           f"epochs={len(n_train_steps)} valid_metrics[-1]={epoch_log['valid_metrics'][-1]} test={test_metrics}")
+
+
+# --------------------------------------------------------------------------- #
+# (i'') mf_small's first epoch again, with torch's CPU square root taken from NumPy.  Adam's square roots are the one
+#       primitive of that run whose last bit depends on the processor: torch takes them from MKL, which picks its code
+#       path per processor vendor whatever MKL_CBWR asks for.  With the IEEE square root in its place the run gives the
+#       same bits on every x86 processor, and the torch-CPU port (oracle/mf_torch_cpu.py) is compared with it bit for
+#       bit on any machine (tests/test_oracle_golden.py, with the same square root).
+# --------------------------------------------------------------------------- #
+def ieee_sqrt(self):
+    return torch.from_numpy(np.sqrt(self.detach().numpy()))
+
+
+def golden_mf_port(out_path):
+    tmp = os.path.join(tempfile.mkdtemp(), "mf_small.npz")
+    mkl_sqrt, torch.Tensor.sqrt = torch.Tensor.sqrt, ieee_sqrt
+    try:
+        golden_mf(tmp)
+    finally:
+        torch.Tensor.sqrt = mkl_sqrt
+    a, g = np.load(tmp), np.load(os.path.join(HERE, "mf_small.npz"))
+    for k in ("U0", "I0", "train_steps", "train_batch_sizes", "train_u", "train_p", "train_n"):
+        assert np.array_equal(a[k], g[k]), k             # the run of mf_small.npz: the same inputs, bit for bit
+    n0 = int(a["train_steps"][0])
+    np.savez_compressed(out_path, versions=VERSIONS, train_step_loss=a["train_step_loss"][:n0],
+                        train_epoch_loss=a["train_epoch_loss"][:1], U_epoch0=a["U_epoch0"])
+    print(f"[mf_port] {n0} steps, epoch loss {a['train_epoch_loss'][0]}")
 
 
 # --------------------------------------------------------------------------- #
@@ -700,10 +728,12 @@ def golden_metric(out_path):
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["mf", "ngcf", "cdae", "metric"]
+    which = sys.argv[1:] or ["mf", "mf_port", "ngcf", "cdae", "metric"]
     torch.set_num_threads(8)
     if "mf" in which:
         golden_mf(os.path.join(HERE, "mf_small.npz"))
+    if "mf_port" in which:
+        golden_mf_port(os.path.join(HERE, "mf_port.npz"))
     if "mf_full" in which:                       # ~20 min: only when named (python make_golden.py mf_full)
         golden_mf_full(os.path.join(HERE, "mf_full.npz"))
     if "ngcf" in which:
