@@ -195,3 +195,39 @@ def test_evaluation_full_size_every_form_gives_the_same_lists(device):
     got = split.cpu().numpy()
     for r in rows:
         assert not set(got[r].tolist()) & set(lists[r].tolist())
+
+
+def test_evaluation_full_size_certified_ladder_rows_equal_float64(device):
+    """The same size and forms as test_evaluation_full_size_every_form_gives_the_same_lists, with 512 certified ladder
+    rows (tests/eval_ladders.py: planted items whose top-10 is unique to within the stated error bound, cancellation,
+    ties and masks among them) planted among Yelp2018-shaped random rows: every form must return the float64 lists
+    of those rows exactly."""
+    import eval_ladders as el
+    from yelprecommendation_amd import engine
+    k = 10
+    case = el.build_case(D, NI, 512, k, seed=29, mask_values=(el.MASK_VALUE,), slice_rows=NU, distractor_scale=0.1,
+                           prescan_place=True)
+    rs = np.random.RandomState(31)
+    Uh = (rs.standard_normal((NU, D)) * 0.1).astype(np.float32)
+    rows = np.sort(rs.choice(NU, 512, replace=False))
+    Uh[rows] = case.U[case.users]
+    lists = [np.unique(rs.randint(0, NI, c)) for c in rs.randint(10, 85, NU)]
+    for q, r in enumerate(rows):
+        lists[r] = case.masks[q]
+    ptr = np.zeros(NU + 1, np.int64)
+    ptr[1:] = np.cumsum([len(m) for m in lists])
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    U, I, users = t(Uh), t(case.I), torch.arange(NU, device=device)
+    p, x = t(ptr), t(np.concatenate(lists).astype(np.int64))
+    want = case.expected[el.MASK_VALUE]
+    base = engine.mf_eval_topk(U, I, users, p, x, k, precision="f32", prescan=False)
+    split = engine.mf_eval_topk(U, I, users, p, x, k, precision="bf16x3", prescan=False)
+    for name, got in (("f32", base), ("bf16x3", split)):
+        assert np.array_equal(got.cpu().numpy()[rows], want), name
+    for kw in (dict(precision="f32", prescan=True), dict(prescan=True), dict(hint=split), dict(hint=base),
+               dict(sliced=False), dict(hint=engine.mf_eval_topk(U * 1.02 + 0.003, I, users, p, x, k)),
+               dict(form="two_roles", prescan=False), dict(form="two_roles", prescan=True),
+               dict(form="two_roles", hint=base), dict(form="four_waves", hint=base)):
+        got = engine.mf_eval_topk(U, I, users, p, x, k, **kw).cpu().numpy()[rows]
+        bad = np.flatnonzero((got != want).any(axis=1))
+        assert len(bad) == 0, f"{kw}: {len(bad)} ladder rows differ, first {bad[:1]}"
