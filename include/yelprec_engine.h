@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define YR_ENGINE_VERSION 28
+#define YR_ENGINE_VERSION 29
 
 #define YR_ERR_UNSUPPORTED (-1) /* embedding width / option not compiled in   */
 #define YR_ERR_BADARG      (-2) /* null pointer, negative size, misalignment  */
@@ -355,7 +355,7 @@ int yr_ngcf_bpr_step(const int32_t *rowptr, const int32_t *col, const float *val
  *
  * yr_gemm_f32: C[M,N] (+)= op(A)[M,K] . op(B)[K,N] on v_mfma_f32_32x32x2_f32 (exact f32), row-major,
  *   transA/transB select A(m,k) = A[k*lda+m] / B(k,n) = B[n*ldb+k].  Plain store epilogue:
- *   C = act(acc + bias[n]) (bias may be NULL; act 0 = identity, 1 = sigmoid).  With split_k > 1 or
+ *   C = act(acc + bias[n]) (bias may be NULL; act 0 = identity, 1 = sigmoid, 2 = ReLU).  With split_k > 1 or
  *   accumulate != 0 the partial products are added atomically into C (caller pre-fills C; bias/act
  *   must then be NULL/0).  Replaces nn.Linear forward (x @ W^T + b: transB = 1), its input gradient
  *   (dy @ W) and its weight gradient (dy^T @ x: transA = 1).
@@ -731,6 +731,47 @@ int yr_triplet_sample(const int64_t *row_user, const int64_t *row_item, int64_t 
                       int64_t first, int64_t count,
                       int64_t *user_out, int64_t *pos_out, int64_t *neg_out,
                       int32_t *err_flag, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * DCN                         (reference models/dcn.py:41-62, loss.py:25-27, trainers/dcn_trainer.py:102-165)
+ * Input rows x0 = [U[user] | I[item] | mean_j C[cat_ids[a, j]] | S[sc_ids[a]]]  (F = 4 D; the mean divides by
+ * the padded length Lmax and includes the padding slot 0).  cat_ids [num_items, Lmax] / sc_ids [num_items] int32
+ * (attr_per_row != 0: one entry per ROW instead, a = row).
+ * yr_dcn_assemble: x (ldx) for B rows (user[b], item_a[b]), or 2B rows with item_b (rows [B, 2B): user[b],
+ *   item_b[b] — the pos / neg rows of a triplet batch side by side).  user == NULL: the item-only rows
+ *   [I[item] | mean C | S] (3 D wide); item_a == NULL: item = row (x_item of every item).  Bad ids raise
+ *   YR_FLAG_BAD_USER / YR_FLAG_BAD_ITEM and leave zeros.
+ * yr_dcn_assemble_bwd: the dense scatter-add of dx into gU / gI / gC / gS (dx / Lmax into every category slot).
+ * yr_relu_bwd: g[e] = y[e] > 0 ? g[e] : 0 in place (y the post-ReLU activation).
+ * yr_dcn_head: per unit (bpr: a triplet, rows b and units + b; else a row) the cross network in closed form
+ *   (x_l = alpha_l x0 + beta_l), the output layer over [h | x_L] (Wo [H + F], bo [1]), the sigmoid; bpr:
+ *   loss_partials (YR_LOSS_PARTIALS, finish with yr_loss_finalize(1 / B)) of -logsigmoid(pred_pos - pred_neg);
+ *   pred (may be NULL) receives the sigmoid outputs.  dx0 != NULL: backward with dpred = the BPR gradient scaled by
+ *   inv_batch (bpr) or gpred[r]: dh = d h (ReLU' applied), dx0 = the cross network's part of d x0 (stored), and
+ *   dcw / dcb [L, F], dWo [H + F], dbo [1] accumulated.  F <= 512, H <= 1024, L <= 8 (YR_ERR_UNSUPPORTED beyond).
+ * yr_dcn_score: scores[r, i] = sigmoid output of (users[r], i) for every item, with the first layer split over the
+ *   concatenation: Au [num_users, H1] = U W1[:, :D]^T, Bi [num_items, H1] = x_item W1[:, D:]^T + b1 (ldbi a
+ *   multiple of 4, 16-byte aligned), Pu [num_users, L + 1] / Pi [num_items, L + 1] the same split of
+ *   x0 . w_l (l < L) and x0 . W_oc.  W2 [H2, H1] / b2 for two hidden layers (the second on the matrix cores), NULL
+ *   for one.  H1, H2 multiples of 32, <= 1024.  Feed the scores to yr_topk_masked with mask_value 0.
+ * ------------------------------------------------------------------------- */
+int yr_dcn_assemble(const float *U, const float *I, const float *C, const float *S, const int32_t *cat_ids,
+                    const int32_t *sc_ids, int Lmax, int D, int64_t num_users, int64_t num_items, int64_t num_cats,
+                    int64_t num_sc, const int64_t *user, const int64_t *item_a, const int64_t *item_b, int64_t B,
+                    int attr_per_row, float *x, int64_t ldx, int32_t *err_flag, void *stream);
+int yr_dcn_assemble_bwd(const float *dx, int64_t ldx, const int32_t *cat_ids, const int32_t *sc_ids, int Lmax, int D,
+                        int64_t num_users, int64_t num_items, int64_t num_cats, int64_t num_sc, const int64_t *user,
+                        const int64_t *item_a, const int64_t *item_b, int64_t B, int attr_per_row, float *gU,
+                        float *gI, float *gC, float *gS, int32_t *err_flag, void *stream);
+int yr_relu_bwd(float *g, const float *y, int64_t n, void *stream);
+int yr_dcn_head(const float *x0, int64_t ldx, const float *h, int64_t ldh, int64_t units, int F, int H, int L,
+                const float *cw, const float *cb, const float *Wo, const float *bo, int bpr, float inv_batch,
+                float *pred, const float *gpred, float *dh, int64_t lddh, float *dx0, int64_t lddx, float *dcw,
+                float *dcb, float *dWo, float *dbo, float *loss_partials, void *stream);
+int yr_dcn_score(const float *Au, int64_t ldau, const float *Bi, int64_t ldbi, const float *Pu, const float *Pi,
+                 const int64_t *users, int64_t n_eval, int64_t num_users, int64_t num_items, int H1, int H2,
+                 const float *W2, const float *b2, const float *Wo, const float *bo, const float *cw, const float *cb,
+                 int L, int F, float *scores, int64_t row_stride, int32_t *err_flag, void *stream);
 
 #ifdef __cplusplus
 }

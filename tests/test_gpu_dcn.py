@@ -1,0 +1,380 @@
+"""GPU parity for DCN: the input assembly (forward / scatter backward / bad ids), the ReLU epilogue of yr_gemm_f32,
+the fused head against float64 autograd of the reference's einsum form, a whole training step and a trainer replay
+against the reference's capture (tests/golden/dcn_small.npz), the fused catalogue scorer against float64 and against
+an unfused GPU route at Yelp2018 shape, checkpoints, and the shapes the kernels refuse."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import dcn_ref
+from dcn_ties import assert_topk_equal_up_to_near_ties, masked_rows
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def g(golden_dir):
+    return np.load(os.path.join(golden_dir, "dcn_small.npz"))
+
+
+def _state(g, prefix):
+    return {k.split(":", 1)[1]: g[k] for k in g.files if k.startswith(prefix + ":")}
+
+
+def _cfg(g, **kw):
+    from yelprecommendation_amd.utils import make_config
+    names, v = list(g["cfg_names"]), g["cfg_values"]
+    base = dict(device="cuda", embed_size=int(v[names.index("embed_size")]), hidden_dims=g["hidden_dims"].tolist(),
+                cross_orders=int(v[names.index("cross_orders")]), lr=float(v[names.index("lr")]),
+                batch_size=int(v[names.index("batch_size")]), epochs=int(v[names.index("epochs")]), top_n=10)
+    base.update(kw)
+    return make_config("DCN", **base)
+
+
+def _trainer(g, tmp_path, prefix="init"):
+    from yelprecommendation_amd.trainers.dcn_trainer import DCNTrainer
+    cfg = _cfg(g, model_dir=str(tmp_path))
+    tr = DCNTrainer(cfg, int(g["num_items"]), int(g["num_users"]), None, g["attributes_count"].tolist(),
+                    cat_ids=torch.from_numpy(g["cat_ids"]), sc_ids=torch.from_numpy(g["sc_ids"]))
+    tr.model.load_state_dict({k: torch.from_numpy(v) for k, v in _state(g, prefix).items()})
+    return tr
+
+
+def _rand_model(D, hidden, L, nu, ni, nc, ns, Lmax, seed):
+    rs = np.random.RandomState(seed)
+    F = 4 * D
+    st = {"user_embedding.weight": rs.standard_normal((nu, D)) * 0.3,
+          "item_embedding.weight": rs.standard_normal((ni, D)) * 0.3,
+          "attributes_embeddings.0.weight": rs.standard_normal((nc, D)) * 0.3,
+          "attributes_embeddings.1.weight": rs.standard_normal((ns, D)) * 0.3}
+    dims = [F] + list(hidden)
+    for k in range(len(hidden)):
+        st[f"deep.{2 * k}.weight"] = rs.standard_normal((dims[k + 1], dims[k])) / np.sqrt(dims[k])
+        st[f"deep.{2 * k}.bias"] = rs.standard_normal(dims[k + 1]) * 0.1
+    for l in range(L):
+        st[f"cross_weights.{l}"] = rs.rand(F) * 0.05
+    for l in range(L):
+        st[f"cross_bias.{l}"] = rs.rand(F) * 0.05
+    st["output_layer.weight"] = rs.standard_normal((1, dims[-1] + F)) / np.sqrt(dims[-1] + F)
+    st["output_layer.bias"] = np.array([0.05])
+    lens = rs.randint(1, Lmax + 1, ni)
+    cat = np.zeros((ni, Lmax), np.int32)
+    for i, n in enumerate(lens):
+        cat[i, :n] = rs.randint(1, nc, n)
+    cat[0] = 0                                               # an all-padding row
+    sc = rs.randint(0, ns, ni).astype(np.int32)
+    return {k: v.astype(np.float32) for k, v in st.items()}, cat, sc
+
+
+def _model(st, cat, sc, D, hidden, L, dev):
+    from yelprecommendation_amd.models.dcn import DCN
+    from yelprecommendation_amd.utils import make_config
+    nu, ni = st["user_embedding.weight"].shape[0], st["item_embedding.weight"].shape[0]
+    cnt = [st["attributes_embeddings.0.weight"].shape[0] - 1, st["attributes_embeddings.1.weight"].shape[0] - 1]
+    m = DCN(make_config("DCN", device="cuda", embed_size=D, hidden_dims=list(hidden), cross_orders=L), nu, ni, cnt)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
+    m = m.to(dev)
+    m.set_item_attributes(torch.from_numpy(cat), torch.from_numpy(sc))
+    return m
+
+
+# ----------------------------------------------------------------------------------------------- assembly
+def test_assembly_forward_backward_and_flags(device):
+    from yelprecommendation_amd import engine
+    D, nu, ni, nc, ns, Lmax = 32, 40, 50, 12, 5, 6
+    st, cat, sc = _rand_model(D, [64], 1, nu, ni, nc, ns, Lmax, 1)
+    P = dcn_ref.params64(st)
+    rs = np.random.RandomState(2)
+    B = 77
+    u = rs.randint(0, nu, B); p = rs.randint(0, ni, B); n = rs.randint(0, ni, B)
+    u[:5] = 3; p[:5] = 0; n[:5] = 0                          # duplicates, all-padding item
+    T = {k: torch.from_numpy(v).to(device) for k, v in st.items()}
+    attrs = (torch.from_numpy(cat).to(device), torch.from_numpy(sc).to(device), nc, ns)
+    tu, tp, tn = (torch.from_numpy(a.astype(np.int64)).to(device) for a in (u, p, n))
+    flag = engine.new_error_flag(device)
+    x = engine.dcn_assemble(T["user_embedding.weight"], T["item_embedding.weight"],
+                            T["attributes_embeddings.0.weight"], T["attributes_embeddings.1.weight"], attrs, tu, tp, tn,
+                            err_flag=flag)
+    want = dcn_ref.x0_rows(P, np.r_[u, u], np.r_[p, n], cat, sc)
+    np.testing.assert_allclose(x.cpu().numpy(), want.detach().numpy(), rtol=1e-6, atol=1e-6)
+    assert int(flag.item()) == 0
+    G = np.random.RandomState(3).standard_normal(x.shape).astype(np.float32)
+    grads = [torch.zeros_like(T[k]) for k in ("user_embedding.weight", "item_embedding.weight",
+                                              "attributes_embeddings.0.weight", "attributes_embeddings.1.weight")]
+    engine.dcn_assemble_bwd(torch.from_numpy(G).to(device), attrs, tu, tp, tn, *grads, nu, err_flag=flag)
+    (want * torch.from_numpy(G.astype(np.float64))).sum().backward()
+    for t, k in zip(grads, ("user_embedding.weight", "item_embedding.weight", "attributes_embeddings.0.weight",
+                            "attributes_embeddings.1.weight")):
+        np.testing.assert_allclose(t.cpu().numpy(), P[k].grad.numpy(), rtol=1e-5, atol=1e-5, err_msg=k)
+    assert float(grads[2][0].abs().sum()) > 0                # the padding row is trained
+    # item-only rows (x_item of the catalogue)
+    xi = engine.dcn_assemble(None, T["item_embedding.weight"], T["attributes_embeddings.0.weight"],
+                             T["attributes_embeddings.1.weight"], attrs, None, None)
+    xi_want = dcn_ref.x0_rows(P, np.zeros(ni, int), np.arange(ni), cat, sc).detach().numpy()[:, D:]
+    np.testing.assert_allclose(xi.cpu().numpy(), xi_want, rtol=1e-6, atol=1e-6)
+    # bad ids: flagged, nothing read out of range
+    bad_u, bad_i = tu.clone(), tp.clone()
+    bad_u[3] = nu
+    engine.dcn_assemble(T["user_embedding.weight"], T["item_embedding.weight"], T["attributes_embeddings.0.weight"],
+                        T["attributes_embeddings.1.weight"], attrs, bad_u, tp, err_flag=flag)
+    assert int(flag.item()) == engine.FLAG_BAD_USER
+    flag.zero_()
+    bad_i[4] = -1
+    engine.dcn_assemble(T["user_embedding.weight"], T["item_embedding.weight"], T["attributes_embeddings.0.weight"],
+                        T["attributes_embeddings.1.weight"], attrs, tu, bad_i, err_flag=flag)
+    assert int(flag.item()) == engine.FLAG_BAD_ITEM
+
+
+# ----------------------------------------------------------------------------------------------- ReLU epilogue
+@pytest.mark.parametrize("tA", [False, True])
+@pytest.mark.parametrize("tB", [False, True])
+@pytest.mark.parametrize("M,N,K", [(1, 1, 1), (70, 167, 33), (256, 128, 64), (130, 65, 64)])
+def test_gemm_relu_epilogue(device, tA, tB, M, N, K):
+    from yelprecommendation_amd import engine
+    rs = np.random.RandomState(M + N + K)
+    A = rs.standard_normal((K, M) if tA else (M, K)).astype(np.float32)
+    B = rs.standard_normal((N, K) if tB else (K, N)).astype(np.float32)
+    bias = rs.standard_normal(N).astype(np.float32)
+    a64 = (A.T if tA else A).astype(np.float64)
+    b64 = (B.T if tB else B).astype(np.float64)
+    want = np.maximum(a64 @ b64 + bias, 0.0)
+    got = engine.gemm_f32(torch.from_numpy(A).to(device), torch.from_numpy(B).to(device), transA=tA, transB=tB,
+                          bias=torch.from_numpy(bias).to(device), act=engine.ACT_RELU).cpu().numpy()
+    np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-5 * np.sqrt(K))
+    assert (got >= 0).all()
+
+
+# ----------------------------------------------------------------------------------------------- fused head
+@pytest.mark.parametrize("D", [16, 32, 64, 128])
+@pytest.mark.parametrize("L", [1, 3, 8])
+def test_fused_head_matches_float64_autograd(device, D, L):
+    from yelprecommendation_amd import engine
+    rs = np.random.RandomState(D * 10 + L)
+    F, H, B = 4 * D, 96, 45
+    x = (rs.standard_normal((2 * B, F)) * 0.2).astype(np.float32)
+    h = np.maximum(rs.standard_normal((2 * B, H)), 0).astype(np.float32)
+    cw = (rs.rand(L, F) * 0.02).astype(np.float32)
+    cb = (rs.rand(L, F) * 0.02).astype(np.float32)
+    Wo = (rs.standard_normal(H + F) * 0.05).astype(np.float32)
+    bo = np.array([0.1], np.float32)
+    t = lambda a: torch.from_numpy(a).to(device)
+    dh, dx = torch.empty(2 * B, H, device=device), torch.empty(2 * B, F, device=device)
+    dcw, dcb = torch.zeros(L, F, device=device), torch.zeros(L, F, device=device)
+    dWo, dbo = torch.zeros(H + F, device=device), torch.zeros(1, device=device)
+    part = torch.zeros(engine.LOSS_PARTIALS, device=device)
+    pred = torch.empty(2 * B, device=device)
+    engine.dcn_head(t(x), t(h), t(cw), t(cb), t(Wo), t(bo), True, inv_batch=1.0 / B, pred=pred,
+                    grads=(dh, dx, dcw, dcb, dWo, dbo), loss_partials=part)
+    loss = engine.loss_finalize(part, 1.0 / B)
+    X, Hh = torch.tensor(x, dtype=torch.float64, requires_grad=True), torch.tensor(h, dtype=torch.float64, requires_grad=True)
+    P = {f"cross_weights.{l}": torch.tensor(cw[l], dtype=torch.float64, requires_grad=True) for l in range(L)}
+    P.update({f"cross_bias.{l}": torch.tensor(cb[l], dtype=torch.float64, requires_grad=True) for l in range(L)})
+    P["output_layer.weight"] = torch.tensor(Wo[None], dtype=torch.float64, requires_grad=True)
+    P["output_layer.bias"] = torch.tensor(bo, dtype=torch.float64, requires_grad=True)
+    pr = dcn_ref.head(P, X, Hh)
+    ref_loss = torch.mean(-torch.nn.functional.logsigmoid(pr[:B] - pr[B:]))
+    ref_loss.backward()
+    np.testing.assert_allclose(pred.cpu().numpy(), pr.detach().numpy(), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(float(loss.item()), float(ref_loss.detach()), rtol=1e-5)
+    gh = Hh.grad.numpy() * (h > 0)
+    np.testing.assert_allclose(dh.cpu().numpy(), gh, rtol=1e-4, atol=1e-7)
+    np.testing.assert_allclose(dx.cpu().numpy(), X.grad.numpy(), rtol=1e-4, atol=1e-4 * np.abs(X.grad.numpy()).max())
+    for l in range(L):
+        for name, got in ((f"cross_weights.{l}", dcw[l]), (f"cross_bias.{l}", dcb[l])):
+            w = P[name].grad.numpy()
+            np.testing.assert_allclose(got.cpu().numpy(), w, rtol=1e-4, atol=1e-4 * np.abs(w).max(), err_msg=name)
+    w = P["output_layer.weight"].grad.numpy()[0]
+    np.testing.assert_allclose(dWo.cpu().numpy(), w, rtol=1e-4, atol=1e-4 * np.abs(w).max())
+    np.testing.assert_allclose(dbo.cpu().numpy(), P["output_layer.bias"].grad.numpy(), rtol=1e-4, atol=1e-8)
+
+
+def test_head_refuses_unsupported_shapes(device):
+    from yelprecommendation_amd import engine
+    z = lambda *s: torch.zeros(*s, device=device)
+    with pytest.raises(engine.EngineError):
+        engine.dcn_head(z(4, 64), z(4, 32), z(9, 64), z(9, 64), z(96), z(1), False, pred=z(4))     # L = 9
+    with pytest.raises(engine.EngineError):
+        engine.dcn_head(z(4, 64), z(4, 2048), z(1, 64), z(1, 64), z(2048 + 64), z(1), False, pred=z(4))
+
+
+# ----------------------------------------------------------------------------------------------- whole step / replay
+def test_whole_step_matches_reference_probe(g, device, tmp_path):
+    tr = _trainer(g, tmp_path)
+    m = tr.model
+    u, p, n = (torch.from_numpy(g[k].astype(np.int64)).to(device) for k in ("probe_u", "probe_p", "probe_n"))
+    cats, sc = torch.from_numpy(g["cat_ids"]), torch.from_numpy(g["sc_ids"])
+    pos = m(u, p, cats[p.cpu()].to(device), sc[p.cpu()].to(device))
+    np.testing.assert_allclose(pos.detach().cpu().numpy().reshape(-1), g["probe_pos"], rtol=1e-5, atol=1e-6)
+    loss = m.bpr_loss_backward(u, p, n)
+    np.testing.assert_allclose(float(loss.item()), float(g["probe_loss"]), rtol=1e-5)
+    for k, prm in m.named_parameters():
+        want = g["grad:" + k]
+        np.testing.assert_allclose(prm.grad.cpu().numpy(), want, rtol=1e-3, atol=1e-4 * max(1e-3, np.abs(want).max()),
+                                   err_msg=k)
+    tr._optimizer_step()
+    lr = tr.cfg.lr
+    for k, v in m.state_dict().items():
+        tiny = np.abs(g["grad:" + k]) < 1e-6
+        np.testing.assert_allclose(v.cpu().numpy()[~tiny], g["step1:" + k][~tiny], rtol=1e-5, atol=2e-6, err_msg=k)
+        np.testing.assert_allclose(v.cpu().numpy()[tiny], g["step1:" + k][tiny], atol=1.01 * lr, err_msg=k)
+    # the autograd forward gives the same gradients as the fused step
+    m.zero_grad(set_to_none=True)
+    tr2 = _trainer(g, tmp_path)
+    cp, sp = cats[p.cpu()].to(device), sc[p.cpu()].to(device)
+    cn, sn = cats[n.cpu()].to(device), sc[n.cpu()].to(device)
+    l2 = tr2.loss(tr2.model(u, p, cp, sp), tr2.model(u, n, cn, sn))
+    l2.backward()
+    for k, prm in tr2.model.named_parameters():
+        want = g["grad:" + k]
+        np.testing.assert_allclose(prm.grad.cpu().numpy(), want, rtol=1e-3, atol=1e-4 * max(1e-3, np.abs(want).max()),
+                                   err_msg=k)
+
+
+def test_trainer_replay_matches_reference(g, device, tmp_path):
+    tr = _trainer(g, tmp_path)
+    tsz, vsz = g["train_batch_sizes"], g["valid_batch_sizes"]
+    tsteps, vsteps = g["train_steps"], g["valid_steps"]
+    got, ta, va = [], 0, 0
+    for e in range(len(tsteps)):
+        sizes = tsz[ta:ta + tsteps[e]]
+        start = int(tsz[:ta].sum())
+        for s in sizes:
+            sl = slice(start, start + int(s))
+            u, p, n = (torch.from_numpy(g[f"train_{c}"][sl].astype(np.int64)).to(device) for c in "upn")
+            got.append(float(tr.model.bpr_loss_backward(u, p, n).item()))
+            tr._optimizer_step()
+            start += int(s)
+        ta += tsteps[e]
+        vstart = int(vsz[:va].sum())
+        vb = []
+        for s in vsz[va:va + vsteps[e]]:
+            vb.append({k: torch.from_numpy(g[f"valid_{c}"][vstart:vstart + int(s)].astype(np.int64))
+                       for k, c in (("user_id", "u"), ("pos_item", "p"), ("neg_item", "n"))})
+            vstart += int(s)
+        va += vsteps[e]
+        np.testing.assert_allclose(tr.validate(vb), g["valid_epoch_loss"][e], rtol=1e-5)
+    np.testing.assert_allclose(got, g["train_step_loss"], rtol=1e-5)
+
+
+@pytest.mark.parametrize("mode", ["valid", "test"])
+def test_evaluation_top10_on_reference_best_weights(g, device, tmp_path, mode):
+    import pandas as pd
+    tr = _trainer(g, tmp_path, prefix="best")
+    users = g[f"{mode}_eval_users"]
+    pp, pi, mp, mi = (g[f"{mode}_{k}"] for k in ("pos_ptr", "pos_idx", "mask_ptr", "mask_idx"))
+    frame = pd.DataFrame({"pos_items": [pi[pp[r]:pp[r + 1]].tolist() for r in range(len(users))],
+                          "mask_items": [mi[mp[r]:mp[r + 1]].tolist() for r in range(len(users))]},
+                         index=pd.Index(users, name="user_id"))
+    metrics = tr.evaluate(frame, mode)
+    _, actual, tu, mptr, midx, _, _ = tr._eval_arrays(frame, 1000 if mode == "valid" else None)
+    got = tr.recommend(tu, mptr, midx).cpu().numpy()
+    want = g[f"top10_{mode}"]
+    P = dcn_ref.params64(_state(g, "best"))
+    s64 = masked_rows(dcn_ref.score_rows(P, users, g["cat_ids"], g["sc_ids"], int(g["num_items"])), mp, mi)
+    clean = assert_topk_equal_up_to_near_ties(got, want, s64, 10)
+    np.testing.assert_allclose(g[f"top10_{mode}_scores"], s64[np.arange(len(users))[:, None], want], rtol=1e-5, atol=1e-6)
+    from yelprecommendation_amd.metric import ranking_metrics
+    if len(clean) == len(users):
+        want_m = g["test_metrics"] if mode == "test" else None
+        if want_m is not None:
+            np.testing.assert_allclose(metrics, want_m, rtol=1e-9, atol=1e-12)
+    if len(clean):                                          # rows with no tie across the 10th place agree exactly
+        sub = [actual[r] for r in clean]
+        np.testing.assert_allclose(ranking_metrics(sub, got[clean].tolist(), 10),
+                                   ranking_metrics(sub, want[clean].tolist(), 10))
+
+
+# ----------------------------------------------------------------------------------------------- fused scorer
+@pytest.mark.parametrize("hidden", [[64], [96, 64], [32, 160]])
+@pytest.mark.parametrize("L", [1, 3])
+def test_scorer_small_shapes_match_float64(device, hidden, L):
+    D, nu, ni = 16, 23, 77                                  # neither a multiple of the 8 x 32 tile
+    st, cat, sc = _rand_model(D, hidden, L, nu, ni, 9, 4, 3, 11 * L + len(hidden))
+    m = _model(st, cat, sc, D, hidden, L, device)
+    users = np.array([0, 5, 22, 7, 7, 13, 1, 2, 3, 4, 6, 9, 19], np.int64)
+    out = torch.empty(len(users), ni, device=device)
+    m.score_catalogue(torch.from_numpy(users).to(device), out)
+    m.check_indices()
+    want = dcn_ref.score_rows(dcn_ref.params64(st), users, cat, sc, ni)
+    np.testing.assert_allclose(out.cpu().numpy(), want, rtol=2e-5, atol=2e-6)
+
+
+def test_scorer_yelp_shape_matches_unfused_gpu_route(device):
+    """Yelp2018 shape (38,048 items, D = 64, [1024, 1024], L = 1), 64 users: the fused scorer against explicit pair
+    rows (the gather) through yr_gemm_f32 and the head kernel."""
+    from yelprecommendation_amd import engine
+    D, hidden, L, nu, ni = 64, [1024, 1024], 1, 31668, 38048
+    st, cat, sc = _rand_model(D, hidden, L, nu, ni, 811, 463, 10, 5)
+    m = _model(st, cat, sc, D, hidden, L, device)
+    users = torch.from_numpy(np.random.RandomState(0).choice(nu, 64, replace=False).astype(np.int64)).to(device)
+    out = torch.empty(64, ni, device=device)
+    m.score_catalogue(users, out)
+    m.check_indices()
+    items = torch.arange(ni, device=device)
+    ref = torch.empty(64, ni, device=device)
+    attrs = m._attrs()
+    for r in range(64):
+        x0, hs = m._rows_forward(users[r].repeat(ni), items, None, attrs)
+        pred = torch.empty(ni, device=device)
+        m._head(x0, hs, bpr=False, pred=pred)
+        ref[r] = pred
+    np.testing.assert_allclose(out.cpu().numpy(), ref.cpu().numpy(), rtol=1e-5, atol=2e-6)
+
+
+def test_scorer_flags_bad_users(device):
+    D, hidden, L = 16, [64, 32], 1
+    st, cat, sc = _rand_model(D, hidden, L, 10, 40, 5, 3, 2, 1)
+    m = _model(st, cat, sc, D, hidden, L, device)
+    out = torch.empty(2, 40, device=device)
+    m.score_catalogue(torch.tensor([1, 10], device=device), out)
+    with pytest.raises(IndexError):
+        m.check_indices()
+
+
+def test_checkpoint_roundtrip_through_load_best_model(g, device, tmp_path):
+    tr = _trainer(g, tmp_path, prefix="best")
+    ref_sd = {k: torch.from_numpy(v) for k, v in _state(g, "best").items()}
+    torch.save(ref_sd, tmp_path / "best_model.pt")          # a reference-keyed file
+    tr2 = _trainer(g, tmp_path, prefix="init")
+    tr2.load_best_model()
+    for k, v in tr2.model.state_dict().items():
+        np.testing.assert_array_equal(v.cpu().numpy(), ref_sd[k].numpy(), err_msg=k)
+    torch.save(tr.model.state_dict(), tmp_path / "best_model.pt")
+    tr2.load_best_model()
+    u = torch.tensor([0, 1, 2], device=device)
+    out1, out2 = torch.empty(3, int(g["num_items"]), device=device), torch.empty(3, int(g["num_items"]), device=device)
+    tr.model.score_catalogue(u, out1)
+    tr2.model.score_catalogue(u, out2)
+    assert torch.equal(out1, out2)
+
+
+# ----------------------------------------------------------------------------------------------- entry point
+@pytest.mark.parametrize("fast_loader", [True, False])
+def test_train_entry_point(device, tmp_path, fast_loader):
+    """python -m yelprecommendation_amd.train model_name=DCN synthetic=... : pipeline with generated attributes ->
+    loaders (device triplet sampler or DataLoader) -> run() -> load_best_model() -> evaluate(test)."""
+    from yelprecommendation_amd import train
+    metrics = train.main(["model_name=DCN", "synthetic=300x200x12", f"fast_loader={str(fast_loader).lower()}",
+                          "epochs=2", "batch_size=64", "embed_size=16", "hidden_dims=[64,32]", "cross_orders=2",
+                          "device=cuda", f"model_dir={tmp_path}", "lr=0.001"])
+    assert len(metrics) == 4 and all(np.isfinite(m) and 0.0 <= m <= 1.0 for m in metrics)
+    assert os.path.exists(os.path.join(str(tmp_path), "best_model.pt"))
+
+
+def test_autograd_then_fused_step_accumulate(g, device, tmp_path):
+    """Gradients left by the autograd forward (separate per-row tensors for the cross parameters) and those the
+    fused step adds on top of them: the same batch twice gives twice the reference's gradients."""
+    tr = _trainer(g, tmp_path)
+    m = tr.model
+    u, p, n = (torch.from_numpy(g[k].astype(np.int64)).to(device) for k in ("probe_u", "probe_p", "probe_n"))
+    cats, sc = torch.from_numpy(g["cat_ids"]), torch.from_numpy(g["sc_ids"])
+    pc, ps = cats[p.cpu()].to(device), sc[p.cpu()].to(device)
+    nc, ns = cats[n.cpu()].to(device), sc[n.cpu()].to(device)
+    tr.loss(m(u, p, pc, ps), m(u, n, nc, ns)).backward()
+    m.bpr_loss_backward(u, p, n)
+    for k, prm in m.named_parameters():
+        want = 2 * g["grad:" + k]
+        np.testing.assert_allclose(prm.grad.cpu().numpy(), want, rtol=1e-3, atol=1e-4 * max(1e-3, np.abs(want).max()),
+                                   err_msg=k)

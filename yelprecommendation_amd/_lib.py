@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # YR_ENGINE_LIB: measurement hook — an instrumented build of the same sources (scratch/inst_build.sh writes it to
 # a temp directory so that the product objects and library are never overwritten); unset in every product run.
 LIB_PATH = os.environ.get("YR_ENGINE_LIB") or os.path.join(_HERE, "libyelprec_engine.so")
-ENGINE_VERSION = 28
+ENGINE_VERSION = 29
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -110,6 +110,15 @@ SIGNATURES = {
                                  _i64, _p, _p, _p],
     "yr_triplet_sample": [_p, _p, _i64, _p, _p, _i64, _i64, C.c_uint64, C.c_uint64, _int, _i64, _i64,
                           _p, _p, _p, _p, _p],
+    "yr_dcn_assemble": [_p, _p, _p, _p, _p, _p, _int, _int, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _int, _p, _i64,
+                        _p, _p],
+    "yr_dcn_assemble_bwd": [_p, _i64, _p, _p, _int, _int, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _int, _p, _p, _p,
+                            _p, _p, _p],
+    "yr_relu_bwd": [_p, _p, _i64, _p],
+    "yr_dcn_head": [_p, _i64, _p, _i64, _i64, _int, _int, _int, _p, _p, _p, _p, _int, _f, _p, _p, _p, _i64, _p, _i64,
+                    _p, _p, _p, _p, _p, _p],
+    "yr_dcn_score": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _p, _p, _p, _p, _p, _int, _int,
+                     _p, _i64, _p, _p],
 }
 
 _lib = None

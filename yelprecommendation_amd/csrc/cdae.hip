@@ -78,6 +78,7 @@ __global__ __launch_bounds__(kBlock) void gemm_f32_kernel(const float* __restric
         } else {
           float v = acc[reg] + bv;
           if (act == 1) v = 1.0f / (1.0f + expf(-v));
+          else if (act == 2) v = v < 0.0f ? 0.0f : v;
           *dst = v;
         }
       }
@@ -326,6 +327,7 @@ __global__ __launch_bounds__(kBlock) void gemm_f32_tiled_kernel(const float* __r
           } else {
             float v = alpha * acc[a][b][reg] + bvl;
             if (act == 1) v = 1.0f / (1.0f + expf(-v));
+            else if (act == 2) v = v < 0.0f ? 0.0f : v;
             *dst = v;
           }
         }
@@ -622,7 +624,7 @@ extern "C" int yr_gemm_f32_ex(int transA, int transB, int64_t M, int64_t N, int6
   if (M < 0 || N < 0 || K < 0 || M > 0x7fffffff || N > 0x7fffffff || K > 0x7fffffff) return YR_ERR_BADARG;
   if (M == 0 || N == 0) return 0;
   if (!A || !B || !C) return YR_ERR_BADARG;
-  if (act != 0 && act != 1) return YR_ERR_UNSUPPORTED;
+  if (act != 0 && act != 1 && act != 2) return YR_ERR_UNSUPPORTED;
   if (split_k < 1) split_k = 1;
   int kps = (int)((K + split_k - 1) / split_k);
   kps = ((kps + kGemmK - 1) / kGemmK) * kGemmK;                 // whole K-steps per split

@@ -149,3 +149,29 @@ def make_interactions_torch(num_users: int = YELP2018_USERS, num_items: int = YE
             item_id = torch.cat([item_id, add_i])
     key = torch.unique(user_id * num_items + item_id)                       # sorted, de-duplicated
     return torch.div(key, num_items, rounding_mode="floor"), key % num_items
+
+
+def make_item_attributes(num_items: int, num_categories: int = 810, num_statecities: int = 462,
+                         seed: int = 4321, max_categories: int = 10, zipf_a: float = 1.3):
+    """Synthetic ``yelp_item2attributes.json`` content for the DCN path (the reference ships no data; its
+    data_preprocess.py:107-133 writes ``{item_id: {'categories': [ids], 'statecity': id}}`` with about 810 categories
+    and 462 state/city pairs, data_preprocess.py:114,119).
+
+    Every item draws 1 to ``max_categories`` distinct categories and one state/city; category and city popularity are
+    Zipf-skewed.  Ids are relabelled densely in order of first appearance, as the reference's encoder does, so
+    ``nunique == max + 1`` holds for both attributes.  Own RNG (``seed``): the interaction generators above are not
+    touched.  Returns a dict keyed by the item id as a string (the JSON schema)."""
+    rs = np.random.RandomState(seed)
+    cat_w = 1.0 / np.arange(1, num_categories + 1) ** zipf_a
+    cat_w /= cat_w.sum()
+    city_w = 1.0 / np.arange(1, num_statecities + 1) ** zipf_a
+    city_w /= city_w.sum()
+    n_cats = np.minimum(rs.geometric(0.3, size=num_items), max_categories)      # geometric draws are >= 1
+    cities = rs.choice(num_statecities, size=num_items, p=city_w)
+    cat_map, city_map = {}, {}
+    out = {}
+    for it in range(num_items):
+        cats = rs.choice(num_categories, size=int(n_cats[it]), replace=False, p=cat_w)
+        enc = [cat_map.setdefault(int(c), len(cat_map)) for c in cats]
+        out[str(it)] = {"categories": enc, "statecity": city_map.setdefault(int(cities[it]), len(city_map))}
+    return out

@@ -410,7 +410,7 @@ def ngcf_dense_bwd(dEout, Eout, E, Z, W1, W2, dE, dW1, dW2, dZ=None, W1T=None, W
     return dZ
 
 
-ACT_IDENTITY, ACT_SIGMOID = 0, 1
+ACT_IDENTITY, ACT_SIGMOID, ACT_RELU = 0, 1, 2
 COUNT_WORDS, COUNT_SLOTS = 2048, 64        # include/yelprec_engine.h YR_COUNT_WORDS / YR_COUNT_SLOTS
 
 
@@ -1138,3 +1138,109 @@ def sgd_dense(p, g, lr, weight_decay=0.0, zero_grad=False):
     n = p.numel()
     check(lib.yr_sgd_dense(_dev(p, torch.float32, "p"), _dev(g, torch.float32, "g"), n,
                            float(lr), float(weight_decay), 1 if zero_grad else 0, _stream()), "yr_sgd_dense")
+
+
+# ---------------------------------------------------------------------------------------------- DCN
+DCN_MAX_F, DCN_MAX_H, DCN_MAX_L = 512, 1024, 8          # csrc/dcn.hip kDcnMaxF / kDcnMaxH / kDcnMaxL
+
+
+def _dcn_attr_args(attrs):
+    """(cat_ids, sc_ids, Lmax) arguments of yr_dcn_assemble / _bwd.  attrs: (cat_ids int32 [rows, Lmax],
+    sc_ids int32 [rows], num_cats, num_sc)."""
+    cat_ids, sc_ids = attrs[0], attrs[1]
+    return [_dev(cat_ids, torch.int32, "cat_ids"), _dev(sc_ids, torch.int32, "sc_ids"), int(cat_ids.shape[1])]
+
+
+def dcn_assemble(U, I, C, S, attrs, user, item_a, item_b=None, attr_per_row=False, out=None, err_flag=None):
+    """x0 rows [U[user] | I[item] | mean C[cats] | S[sc]] (B rows; 2B with item_b: pos rows then neg rows).
+    ``user=None``: the item-only rows (3 D wide); ``item_a=None``: item = row (x_item of the whole catalogue)."""
+    lib = _lib.load()
+    cat_ids, sc_ids, num_cats, num_sc = attrs
+    D = I.shape[1]
+    B = item_a.numel() if item_a is not None else (I.shape[0] if not attr_per_row else cat_ids.shape[0])
+    rows = 2 * B if item_b is not None else B
+    width = (4 if user is not None else 3) * D
+    if out is None:
+        out = torch.empty((rows, width), dtype=torch.float32, device=I.device)
+    if out.shape[0] < rows or out.shape[1] != width or out.stride(1) != 1:
+        raise EngineError("dcn_assemble: bad output buffer")
+    nu = U.shape[0] if U is not None else 0
+    check(lib.yr_dcn_assemble(_opt(U, torch.float32, "U"), _dev(I, torch.float32, "I"), _dev(C, torch.float32, "C"),
+                              _dev(S, torch.float32, "S"), *_dcn_attr_args(attrs),
+                              D, nu, I.shape[0], int(num_cats), int(num_sc), _opt(user, torch.int64, "user"),
+                              _opt(item_a, torch.int64, "item_a"), _opt(item_b, torch.int64, "item_b"), B,
+                              1 if attr_per_row else 0, out.data_ptr(), out.stride(0), _opt(err_flag, torch.int32, "flag"),
+                              _stream()), "yr_dcn_assemble")
+    return out
+
+
+def dcn_assemble_bwd(dx, attrs, user, item_a, item_b, gU, gI, gC, gS, num_users, attr_per_row=False, err_flag=None):
+    """Dense scatter-add of d x0 into the four table gradients (the category mean hands dx / Lmax to every slot)."""
+    lib = _lib.load()
+    cat_ids, sc_ids, num_cats, num_sc = attrs
+    D = gI.shape[1]
+    B = item_a.numel() if item_a is not None else dx.shape[0]
+    check(lib.yr_dcn_assemble_bwd(_rows(dx, torch.float32, "dx"), dx.stride(0),
+                                  *_dcn_attr_args(attrs), D, int(num_users),
+                                  gI.shape[0], int(num_cats), int(num_sc), _opt(user, torch.int64, "user"),
+                                  _opt(item_a, torch.int64, "item_a"), _opt(item_b, torch.int64, "item_b"), B,
+                                  1 if attr_per_row else 0, _opt(gU, torch.float32, "gU"), _dev(gI, torch.float32, "gI"),
+                                  _dev(gC, torch.float32, "gC"), _dev(gS, torch.float32, "gS"),
+                                  _opt(err_flag, torch.int32, "flag"), _stream()), "yr_dcn_assemble_bwd")
+
+
+def relu_bwd_(g, y):
+    """g <- g * (y > 0) in place (y: the post-ReLU activation)."""
+    lib = _lib.load()
+    if g.shape != y.shape:
+        raise EngineError("relu_bwd: shapes differ")
+    check(lib.yr_relu_bwd(_dev(g, torch.float32, "g"), _dev(y, torch.float32, "y"), g.numel(), _stream()), "yr_relu_bwd")
+    return g
+
+
+def dcn_head(x0, h, cw, cb, Wo, bo, bpr, inv_batch=0.0, pred=None, gpred=None, grads=None, loss_partials=None):
+    """Cross network + output layer + sigmoid (+ BPR loss) over the rows of x0 / h (yr_dcn_head).
+    ``bpr``: rows [0, B) and [B, 2B) are the pos / neg rows of B triplets.  ``grads``: (dh, dx0, dcw, dcb, dWo, dbo)
+    — dh and dx0 are written, the weight gradients accumulated."""
+    lib = _lib.load()
+    f32 = torch.float32
+    rows, F = x0.shape
+    H = h.shape[1]
+    L = cw.shape[0]
+    units = rows // 2 if bpr else rows
+    if h.shape[0] != rows or cw.shape != (L, F) or cb.shape != (L, F) or Wo.numel() != H + F:
+        raise EngineError("dcn_head: inconsistent shapes")
+    dh = dx0 = dcw = dcb = dWo = dbo = None
+    if grads is not None:
+        dh, dx0, dcw, dcb, dWo, dbo = grads
+    check(lib.yr_dcn_head(_rows(x0, f32, "x0"), x0.stride(0), _rows(h, f32, "h"), h.stride(0), units, F, H, L,
+                          _dev(cw, f32, "cw"), _dev(cb, f32, "cb"), _dev(Wo, f32, "Wo"), _dev(bo, f32, "bo"),
+                          1 if bpr else 0, float(inv_batch), _opt(pred, f32, "pred"), _opt(gpred, f32, "gpred"),
+                          None if dh is None else _rows(dh, f32, "dh"), 0 if dh is None else dh.stride(0),
+                          None if dx0 is None else _rows(dx0, f32, "dx0"), 0 if dx0 is None else dx0.stride(0),
+                          _opt(dcw, f32, "dcw"), _opt(dcb, f32, "dcb"), _opt(dWo, f32, "dWo"), _opt(dbo, f32, "dbo"),
+                          _opt(loss_partials, f32, "loss_partials"), _stream()), "yr_dcn_head")
+
+
+def dcn_score(Au, Bi, Pu, Pi, users, W2, b2, Wo, bo, cw, cb, out, err_flag=None):
+    """out[r, i] = the DCN sigmoid output of (users[r], item i) for the whole catalogue (yr_dcn_score); the first
+    hidden layer arrives split as Au (per user) + Bi (per item, bias included), the cross / output dot products of
+    x0 as Pu + Pi.  W2 None: one hidden layer."""
+    lib = _lib.load()
+    f32 = torch.float32
+    n = users.numel()
+    num_users, H1 = Au.shape
+    num_items = Bi.shape[0]
+    L, F = cw.shape
+    H2 = W2.shape[0] if W2 is not None else 0
+    if Pu.shape != (num_users, L + 1) or Pi.shape != (num_items, L + 1) or Bi.shape[1] != H1:
+        raise EngineError("dcn_score: inconsistent shapes")
+    if out.dim() != 2 or out.shape[0] < n or out.shape[1] < num_items or out.stride(1) != 1:
+        raise EngineError("dcn_score: bad output buffer")
+    check(lib.yr_dcn_score(_rows(Au, f32, "Au"), Au.stride(0), _rows(Bi, f32, "Bi"), Bi.stride(0),
+                           _dev(Pu, f32, "Pu"), _dev(Pi, f32, "Pi"), _dev(users, torch.int64, "users"), n, num_users,
+                           num_items, H1, H2, _opt(W2, f32, "W2"), _opt(b2, f32, "b2"), _dev(Wo, f32, "Wo"),
+                           _dev(bo, f32, "bo"), _dev(cw, f32, "cw"), _dev(cb, f32, "cb"), L, F, out.data_ptr(),
+                           out.stride(0) if n > 1 else num_items, _opt(err_flag, torch.int32, "flag"), _stream()),
+          "yr_dcn_score")
+    return out

@@ -51,6 +51,16 @@ def _lists_to_csr(lists):
     return ptr, idx
 
 
+def eval_csr(users, pos, masks, device):
+    """(pos lists, users, mask_ptr, mask_idx, pos_ptr, pos_idx) of an evaluation set on the device: the held-out
+    lists in their original order (the metrics depend on it) and the mask lists as CSR."""
+    mask_ptr, mask_idx = _lists_to_csr(masks)
+    pos_ptr, pos_idx = _lists_to_csr(pos)
+    return (pos, torch.from_numpy(users).to(device), torch.from_numpy(mask_ptr).to(device),
+            torch.from_numpy(mask_idx).to(device), torch.from_numpy(pos_ptr).to(device),
+            torch.from_numpy(pos_idx).to(device))
+
+
 class MFTrainer(BaseTrainer):
     def __init__(self, cfg, num_items: int, num_users: int) -> None:
         super().__init__(cfg)
@@ -297,12 +307,7 @@ class MFTrainer(BaseTrainer):
             if self.world_size > 1:                            # this rank scores the users it owns
                 keep = np.flatnonzero(self.shard.mine(users))
                 users, pos, masks = users[keep], [pos[k] for k in keep], [masks[k] for k in keep]
-            mask_ptr, mask_idx = _lists_to_csr(masks)
-            pos_ptr, pos_idx = _lists_to_csr(pos)
-            dev = self.device
-            self._eval_cache[key] = (eval_data, pos, torch.from_numpy(users).to(dev),
-                                     torch.from_numpy(mask_ptr).to(dev), torch.from_numpy(mask_idx).to(dev),
-                                     torch.from_numpy(pos_ptr).to(dev), torch.from_numpy(pos_idx).to(dev))
+            self._eval_cache[key] = (eval_data,) + eval_csr(users, pos, masks, self.device)
         return self._eval_cache[key][1:5]
 
     def recommend(self, users, mask_ptr, mask_idx, hint_key=None):

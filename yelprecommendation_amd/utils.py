@@ -59,6 +59,7 @@ DEFAULTS = Config(
                   hidden_activation="sigmoid", output_activation="sigmoid"),
         MF=dict(embed_size=64),
         NGCF=dict(embed_size=64, num_orders=2),
+        DCN=dict(embed_size=64, hidden_dims=[1024, 1024], cross_orders=1),
     ),
 )
 
