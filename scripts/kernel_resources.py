@@ -6,8 +6,12 @@ an edit that pushes a kernel over its budget fails the build instead of silently
 (the owner passes need 8 workgroups per CU, the split evaluation kernel 3 waves per SIMD).
 
     python scripts/kernel_resources.py            # table of all kernels + budget check
+    python scripts/kernel_resources.py --isa DIR  # ... and the instruction text of every kernel, one file each, so
+                                                  # that two builds can be compared with `diff -r` (a refactor that
+                                                  # moves code between files must leave them equal)
 """
 import glob
+import hashlib
 import os
 import re
 import shutil
@@ -51,7 +55,26 @@ def _demangle(names):
     return out.strip().split("\n")
 
 
-def read_object(obj):
+def _write_isa(isa_dir, obj, dis):
+    """One file per symbol of the disassembly: instructions and branch targets (symbol + offset), no addresses or
+    encodings — text that stays the same when a kernel merely moves inside its code object."""
+    os.makedirs(isa_dir, exist_ok=True)
+    out = None
+    for line in dis.splitlines():
+        m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+        if m:
+            if out:
+                out.close()
+            sym = m.group(1)          # mangled names can exceed a file name: cut, and keep them apart by a digest
+            out = open(os.path.join(isa_dir, f"{os.path.basename(obj)}.{sym[:120]}.{hashlib.sha1(sym.encode()).hexdigest()[:8]}.s"), "w")
+            out.write(f"<{sym}>:\n")
+        elif out and line.strip():
+            out.write(re.sub(r"\s*// [0-9A-F]+:( [0-9A-F]{8})+", "", line) + "\n")
+    if out:
+        out.close()
+
+
+def read_object(obj, isa_dir=None):
     """{demangled kernel name: dict(vgpr, agpr, sgpr, lds, scratch, spill)} of one .o (gfx950 bundle)."""
     tmp = tempfile.mkdtemp(prefix="yr_kres.")
     try:
@@ -68,6 +91,8 @@ def read_object(obj):
                              check=True).stdout
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+    if isa_dir:
+        _write_isa(isa_dir, obj, dis)
     kernels, cur = [], None
     for line in notes.splitlines():
         m = re.match(r"\s+(-\s+)?\.(\w+):\s+(.*)$", line)
@@ -96,10 +121,10 @@ def read_object(obj):
             for n, k in zip(names, kernels)}
 
 
-def read_all():
+def read_all(isa_dir=None):
     out = {}
     for obj in sorted(glob.glob(os.path.join(CSRC, "*.o"))):
-        for name, r in read_object(obj).items():
+        for name, r in read_object(obj, isa_dir).items():
             r["file"] = os.path.basename(obj)
             out[name] = r
     return out
@@ -130,7 +155,7 @@ def check(kernels=None):
 
 
 if __name__ == "__main__":
-    ks = read_all()
+    ks = read_all(sys.argv[2] if len(sys.argv) == 3 and sys.argv[1] == "--isa" else None)
     for n, r in sorted(ks.items(), key=lambda kv: (kv[1]["file"], kv[0])):
         print(f"{r['file']:18s} vgpr {r['vgpr']:3d} agpr {r['agpr']:3d} sgpr {r['sgpr']:3d} lds {r['lds']:6d} scratch {r['scratch']:4d} ({r['scratch_ops']:2d} ops)  {n[:110]}")
     try:

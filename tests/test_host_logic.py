@@ -17,6 +17,14 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(yr_[a-z0-9_]+)\s*\(", hdr)))
 
 
+def _declared_return_types():
+    """{symbol: return type as written in the header} — every declaration starts a line with its type."""
+    hdr = open(os.path.join(ROOT, "include", "yelprec_engine.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    return {name: " ".join(typ.split()) for typ, name in
+            re.findall(r"^((?:const\s+)?\w+\s*\*?)\s*(yr_[a-z0-9_]+)\s*\(", hdr, flags=re.M)}
+
+
 def test_library_exports_every_declared_symbol():
     """The C-ABI library loads and exports exactly what include/yelprec_engine.h declares
     (no compute calls here: there is no GPU in this container)."""
@@ -28,6 +36,15 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} declared in the header but not exported"
         assert name in _lib.SIGNATURES, f"{name} has no ctypes signature in _lib.py"
     assert sorted(_lib.SIGNATURES) == declared
+    # ... with the return type the header declares (a wrong one truncates a byte count or misreads a pointer)
+    returns = _declared_return_types()
+    assert sorted(returns) == declared
+    ctype_of = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char *": ctypes.c_char_p}
+    assert set(_lib.RESTYPES) <= set(declared)
+    for name in declared:
+        assert returns[name] in ctype_of, f"{name}: return type {returns[name]!r} has no ctypes mapping here"
+        assert getattr(lib, name).restype is ctype_of[returns[name]], f"{name} returns {returns[name]} in the header"
+        assert _lib.RESTYPES.get(name, ctypes.c_int) is ctype_of[returns[name]]
     assert lib.yr_engine_version() == _lib.ENGINE_VERSION
     assert lib.yr_engine_arch() == b"gfx950"
     raw = ctypes.CDLL(_lib.LIB_PATH)

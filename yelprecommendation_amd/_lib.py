@@ -121,6 +121,14 @@ SIGNATURES = {
                      _p, _i64, _p, _p],
 }
 
+# return types: an int status (0, a negative YR_ERR_* or a HIP error) unless listed here — checked against the header by
+# tests/test_host_logic.py, like SIGNATURES
+RESTYPES = {"yr_engine_arch": C.c_char_p}
+RESTYPES.update({name: _i64 for name in (
+    "yr_bpr_mf_pull_workspace_bytes", "yr_rank_metrics_workspace_bytes", "yr_cdae_sparse_part_columns",
+    "yr_cdae_decode_loss_partials", "yr_mf_eval_topk_workspace_bytes", "yr_mf_eval_topk_planes_bytes",
+    "yr_ngcf_step_workspace_bytes")})
+
 _lib = None
 
 
@@ -152,14 +160,7 @@ def load():
         except AttributeError as e:
             raise EngineError(f"{LIB_PATH} does not export {name}") from e
         fn.argtypes = argtypes
-        fn.restype = {"yr_engine_arch": C.c_char_p,
-                      "yr_bpr_mf_pull_workspace_bytes": C.c_int64,
-                      "yr_rank_metrics_workspace_bytes": C.c_int64,
-                      "yr_cdae_sparse_part_columns": C.c_int64,
-                      "yr_cdae_decode_loss_partials": C.c_int64,
-                      "yr_mf_eval_topk_workspace_bytes": C.c_int64,
-                      "yr_mf_eval_topk_planes_bytes": C.c_int64,
-                      "yr_ngcf_step_workspace_bytes": C.c_int64}.get(name, C.c_int)
+        fn.restype = RESTYPES.get(name, C.c_int)
     v = lib.yr_engine_version()
     if v != ENGINE_VERSION:
         raise EngineError(f"engine ABI version {v} != expected {ENGINE_VERSION}; rebuild the library")

@@ -34,7 +34,7 @@ rounding: the 1 / count factor is applied to the products instead of to G.
 """
 import torch
 
-from . import engine
+from . import engine, optim
 
 
 class CDAEStep:
@@ -86,11 +86,7 @@ class CDAEStep:
         self.flag = engine.new_error_flag(dev)
         self._batch = None
         for p in self.params:                                                   # the optimizer's own Adam state
-            st = optimizer.state[p]
-            if not st:
-                st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            optim.adam_state(optimizer, p)
 
     def bound_to(self, model, optimizer):
         """Still bound to these parameter / state tensors (they are replaced by load_state_dict)?"""

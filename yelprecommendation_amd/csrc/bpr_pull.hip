@@ -44,6 +44,7 @@
 // works on GPW = 64/LPR contributions at once; the per-contribution dot product is a reduction
 // over LPR lanes only.  At the end a wave holds GPW consecutive rows, one per lane group: own row,
 // m, v and the Adam update stream 1 KB per wave instruction.
+#include "adam.h"
 #include "common.h"
 
 namespace yr {
@@ -89,25 +90,11 @@ constexpr int kBuildLanes = 4;                   // lanes that share one item bu
 #define YR_OWNER_WAVES 8              // waves per SIMD the owner pass is compiled for (8 workgroups per CU: <= 64 VGPRs)
 #endif
 
-struct AdamC {
-  float decay_mul, neg_step, bc2_sqrt, one_m_b1, beta2, one_m_b2, eps, wd;
-  int decoupled;
+struct PullAdam {
+  AdamScalars c;
+  int decoupled;               // AdamW: a run-time value here, one set of owner-pass kernels for both
 };
 
-__device__ __forceinline__ void adam1(float& p, float grad, float& m, float& v, const AdamC& c) {
-  if (c.wd != 0.0f) {
-    if (c.decoupled) p *= c.decay_mul;
-    else grad = grad + c.wd * p;
-  }
-  m = m + c.one_m_b1 * (grad - m);
-  v = v * c.beta2 + (c.one_m_b2 * grad) * grad;
-  const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
-  p = p + (c.neg_step * m) / denom;
-}
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 // row gathers: uniform base + 32-bit element offset (a table holds at most 16383 buckets x 1024
 // floats), so the address stays one VGPR next to an SGPR pair
 __device__ __forceinline__ float4 ld4o(const float* base, uint32_t off) {
@@ -279,7 +266,7 @@ struct OwnerArgs {
   const int32_t* order;      // optional: workgroup slot -> bucket (a permutation of [0, nb): heaviest buckets first)
   int heavy_t;               // rows with more records in a chunk are walked by all four waves
   float inv_batch;
-  AdamC adam;
+  PullAdam adam;
   // oversize item buckets (see kSplitMin): `split` = the bookkeeping block of the workspace — {tasks, slots}
   // counters (16 B), then parts[nbI], slot[nbI], arrive[nbI] (each padded to 16 B), then the task list.
   // Item pass: the first helper_blocks workgroups are helpers (task j); parts[k] > 1 marks a split bucket whose
@@ -806,10 +793,10 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
       if (FUSE_ADAM) {
         float4 own = USER ? s_own[row_l * LPR + l] : ld4o(a.own_old, o_f);
         float4 M = ld4o(a.m, o_f), V = ld4o(a.v, o_f);
-        adam1(own.x, acc.x, M.x, V.x, a.adam);
-        adam1(own.y, acc.y, M.y, V.y, a.adam);
-        adam1(own.z, acc.z, M.z, V.z, a.adam);
-        adam1(own.w, acc.w, M.w, V.w, a.adam);
+        adam_element(own.x, acc.x, M.x, V.x, a.adam.c, a.adam.decoupled);
+        adam_element(own.y, acc.y, M.y, V.y, a.adam.c, a.adam.decoupled);
+        adam_element(own.z, acc.z, M.z, V.z, a.adam.c, a.adam.decoupled);
+        adam_element(own.w, acc.w, M.w, V.w, a.adam.c, a.adam.decoupled);
         st4(a.own_new + o_f, own);
         st4(a.m + o_f, M);
         st4(a.v + o_f, V);
@@ -977,25 +964,10 @@ extern "C" int yr_bpr_mf_pull_index(const int64_t* user, const int64_t* pos, con
   return launch_status();
 }
 
-static int make_adam(AdamC& c, double lr, double step_size, double bc2_sqrt, double beta1, double beta2, double eps,
-                     double weight_decay, int mode) {
-  if (mode != YR_OPT_ADAM && mode != YR_OPT_ADAMW) return YR_ERR_UNSUPPORTED;
-  c.decay_mul = (float)(1.0 - lr * weight_decay);
-  c.neg_step = (float)(-step_size);
-  c.bc2_sqrt = (float)bc2_sqrt;
-  c.one_m_b1 = (float)(1.0 - beta1);
-  c.beta2 = (float)beta2;
-  c.one_m_b2 = (float)(1.0 - beta2);
-  c.eps = (float)eps;
-  c.wd = (float)weight_decay;
-  c.decoupled = mode == YR_OPT_ADAMW;
-  return 0;
-}
-
 // phase 2: the two owner passes over a partition built by phase 1 for the same batch
 template <int D>
 static int pull_apply_impl(const float* U_old, float* U_new, float* I, float* mU, float* vU, float* mI, float* vI,
-                           float* gradI_out, int64_t B, int64_t nU, int64_t nI, float inv_batch, const AdamC& adam,
+                           float* gradI_out, int64_t B, int64_t nU, int64_t nI, float inv_batch, const PullAdam& adam,
                            int deterministic, void* workspace, float* loss_partials, float* loss_out,
                            double* loss_accum, int phases, int64_t item_begin, int64_t item_end,
                            const int32_t* item_order, hipStream_t s) {
@@ -1090,9 +1062,8 @@ extern "C" int yr_bpr_mf_pull_apply_ordered(const float* U_old, float* U_new, fl
   if (item_row_begin % R != 0 || (item_row_end % R != 0 && item_row_end != num_items)) return YR_ERR_BADARG;
   if (!U_old || !U_new || U_old == U_new || !I || !mU || !vU || !loss_partials) return YR_ERR_BADARG;
   if (!gradI_out && (!mI || !vI)) return YR_ERR_BADARG;
-  AdamC c;
-  rc = make_adam(c, lr, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, mode);
-  if (rc) return rc;
+  if (mode != YR_OPT_ADAM && mode != YR_OPT_ADAMW) return YR_ERR_UNSUPPORTED;
+  const PullAdam c = {adam_scalars(lr, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay), mode == YR_OPT_ADAMW};
   hipStream_t s = (hipStream_t)stream;
 #define YR_APPLY_CASE(DD)                                                                                       \
   case DD:                                                                                                      \

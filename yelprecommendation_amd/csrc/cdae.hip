@@ -7,10 +7,10 @@
 // The two Linear layers and their three gradient products are GEMMs on the matrix cores
 // (v_mfma_f32_32x32x2_f32, exact f32).  Everything else is byte-bound element-wise work.
 #include "common.h"
+#include "philox.h"
 
 namespace yr {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 // --------------------------------------------------------------------------- f32 MFMA GEMM
 // C[M, N] (+)= op(A)[M, K] . op(B)[K, N]     row-major, leading dimensions lda / ldb / ldc
@@ -383,27 +383,13 @@ __global__ __launch_bounds__(kBlock) void dropout_kernel(const float* __restrict
 // nn.Dropout with the uniforms drawn in the kernel: Philox4x32-10 keyed by `seed`, counter = index
 // of the float4 group, so the mask depends on (seed, position) only — no 4-byte-per-element random
 // tensor is written and read back.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += 0x9E3779B9u;
-    key.y += 0xBB67AE85u;
-  }
-  return ctr;
-}
-
-__device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
-
 __global__ __launch_bounds__(kBlock) void dropout_seeded_kernel(const float* __restrict__ x, uint64_t seed, float p,
                                                                 float scale, int64_t n, float* __restrict__ out) {
   const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
   const int64_t n4 = (n + 3) / 4;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < n4; q += stride) {
-    const uint4 r = philox4x32_10(make_uint4((uint32_t)q, (uint32_t)(q >> 32), 0u, 0u), key);
+    const uint4 r = philox4x32<10>(make_uint4((uint32_t)q, (uint32_t)(q >> 32), 0u, 0u), key);
     const float u[4] = {u01(r.x), u01(r.y), u01(r.z), u01(r.w)};
     const int64_t e = 4 * q;
     if (e + 3 < n) {

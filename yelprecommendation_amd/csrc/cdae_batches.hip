@@ -12,23 +12,12 @@
 //                          holds it are ranked in LDS (11 more bits per pass only for rows so long
 //                          that a bin overflows the list).
 #include "common.h"
+#include "philox.h"
 
 namespace yr {
 
-__device__ __forceinline__ uint4 cb_philox(uint4 ctr, uint2 key) {
-#pragma unroll
-  for (int r = 0; r < 7; ++r) {                        // Philox4x32-7 (the shortest variant that passes BigCrush)
-    const uint32_t hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += 0x9E3779B9u;
-    key.y += 0xBB67AE85u;
-  }
-  return ctr;
-}
-
 __device__ __forceinline__ uint64_t cb_key(uint64_t seed, int64_t row, int64_t item) {
-  const uint4 r = cb_philox(make_uint4((uint32_t)item, (uint32_t)(item >> 32), (uint32_t)row, (uint32_t)(row >> 32)),
+  const uint4 r = philox4x32<7>(make_uint4((uint32_t)item, (uint32_t)(item >> 32), (uint32_t)row, (uint32_t)(row >> 32)),
                             make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
   return ((uint64_t)r.x << 32) | r.y;
 }

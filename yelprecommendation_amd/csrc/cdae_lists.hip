@@ -24,27 +24,14 @@
 // non-positives are wanted the EXCLUDED ones are drawn instead.
 // Both lists come out in ascending column order in the 32-sub-list layout of cdae_sparse.hip.
 #include "common.h"
+#include "philox.h"
 
 namespace yr {
 
-constexpr int kListParts = 32;                  // == cdae_sparse.hip kParts
 // one workgroup of 16 waves per row: the row's work (a bitmap scan of the catalogue, 64 columns per wave step) is a
 // chain of short steps, and with 4 waves it ran at one wave per SIMD (41 us per 256 rows; the rows' CUs idle otherwise)
 constexpr int kListThreads = 1024;
 constexpr int kListWaves = kListThreads / kWave;
-
-__device__ __forceinline__ uint4 cl_philox(uint4 ctr, uint2 key, int rounds) {
-  for (int r = 0; r < rounds; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += 0x9E3779B9u;
-    key.y += 0xBB67AE85u;
-  }
-  return ctr;
-}
-
-__device__ __forceinline__ float cl_u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
 
 __global__ __launch_bounds__(kListThreads) void cdae_train_lists_kernel(
     const int64_t* __restrict__ ptr, const int64_t* __restrict__ idx, const int64_t* __restrict__ ptr2,
@@ -131,7 +118,7 @@ __global__ __launch_bounds__(kListThreads) void cdae_train_lists_kernel(
     const int k = min(target - got, kListThreads);
     if (tid < k) {
       const uint64_t d = next + tid;
-      const uint4 w = cl_philox(make_uint4((uint32_t)d, (uint32_t)(d >> 32), (uint32_t)rl, (uint32_t)(rl >> 32)), nkey, 7);
+      const uint4 w = philox4x32_rolled(make_uint4((uint32_t)d, (uint32_t)(d >> 32), (uint32_t)rl, (uint32_t)(rl >> 32)), nkey, 7);
       const uint64_t m = (uint64_t)w.x * span;
       if ((uint32_t)m >= lemire_min) {
         const uint32_t it = (uint32_t)(m >> 32);
@@ -173,9 +160,9 @@ __global__ __launch_bounds__(kListThreads) void cdae_train_lists_kernel(
           for (uint32_t b = in_bits; b; b &= b - 1) {
             const int bit = __ffs((int)b) - 1;
             const int64_t e = rl * I + (((int64_t)w << 5) + bit);   // flat position of the dense batch: its Philox group and word
-            const uint4 wd = cl_philox(make_uint4((uint32_t)(e >> 2), (uint32_t)((e >> 2) >> 32), 0u, 0u), dkey, 10);
+            const uint4 wd = philox4x32_rolled(make_uint4((uint32_t)(e >> 2), (uint32_t)((e >> 2) >> 32), 0u, 0u), dkey, 10);
             const uint32_t word = (e & 3) == 0 ? wd.x : (e & 3) == 1 ? wd.y : (e & 3) == 2 ? wd.z : wd.w;
-            if (cl_u01(word) >= p) enc_bits |= 1u << bit;
+            if (u01(word) >= p) enc_bits |= 1u << bit;
           }
         }
         const uint32_t loss_bits = pos_bits | neg_bits;
@@ -226,7 +213,7 @@ static int train_lists_impl(const int64_t* ptr, const int64_t* idx, const int64_
   const int words = (int)((I + 31) / 32);
   const size_t lds = (size_t)(ptr2 ? 3 : 2) * words * sizeof(uint32_t);
   if (lds > 60 * 1024) return YR_ERR_UNSUPPORTED;        // catalogues beyond ~245 k items: the dense route
-  const int64_t cpp = ((I + kListParts - 1) / kListParts + 3) / 4 * 4;   // == yr_cdae_sparse_part_columns(I)
+  const int64_t cpp = yr_cdae_sparse_part_columns(I);
   hipLaunchKernelGGL(cdae_train_lists_kernel, dim3((unsigned)B), dim3(kListThreads), lds, (hipStream_t)stream, ptr, idx, ptr2,
                      idx2, users, num_users, I, neg_times, neg_seed, drop_seed, (float)p, (float)(1.0 / (1.0 - p)), neg_seeds, drop_seeds,
                      batch_rows, cpp, words,

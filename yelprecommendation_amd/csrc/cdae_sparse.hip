@@ -12,30 +12,16 @@
 //   yr_cdae_sparse_dwh     dW_h[h, col_j] += dz[r, h] val_j                                 (float atomics into
 //                          the zeroed gradient: a few thousand columns are touched per batch).
 #include "common.h"
+#include "philox.h"
 
 namespace yr {
 
-__device__ __forceinline__ uint4 cs_philox4x32_10(uint4 ctr, uint2 key) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += 0x9E3779B9u;
-    key.y += 0xBB67AE85u;
-  }
-  return ctr;
-}
-
-__device__ __forceinline__ float cs_u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
-
-// Row r of x[B, I] is cut into kParts column ranges of `cpp` columns (a multiple of 4); part q's non-zeros go to
-// cols/vals[(r * kParts + q) * cpp ..] in ascending column order, count[r * kParts + q].  One WAVE per (row,
+// Row r of x[B, I] is cut into kListParts column ranges of `cpp` columns (a multiple of 4); part q's non-zeros go to
+// cols/vals[(r * kListParts + q) * cpp ..] in ascending column order, count[r * kListParts + q].  One WAVE per (row,
 // part): 1 KB coalesced loads, wave prefix with shuffles, no barriers (a workgroup per row with block-wide
 // prefixes took 60 us at I = 38,048: 38 dependent load -> scan -> store rounds per row).
 // p > 0: nn.Dropout(p) in training mode with the mask of yr_dropout_seeded(seed) — uniform word k of
 // Philox(counter = flat index / 4) for flat index 4 * (flat / 4) + k.
-constexpr int kParts = 32;
 
 // PAIR: the same pass also lists the LOSS positions of the row, target + negative_mask != 0, as (column, target)
 // (see the sampled decoder below).  The next 1 KB of the row(s) is fetched while the current one is scanned.
@@ -51,7 +37,7 @@ __global__ __launch_bounds__(kBlock) void cdae_compact_rows_kernel(
   const float* row = x + r * I;
   const float* nrow = PAIR ? negmask + r * I : nullptr;
   const int64_t c_lo = (int64_t)part * cpp, c_hi = min(I, c_lo + cpp);
-  const int64_t at0 = (r * kParts + part) * cpp;
+  const int64_t at0 = (r * kListParts + part) * cpp;
   const bool vec = (I & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | (PAIR ? reinterpret_cast<uintptr_t>(negmask) : 0)) & 15) == 0;
   auto fetch = [&](int64_t c, float (&t)[4], float (&m)[4]) {
     if (vec && c + 3 < c_hi) {
@@ -83,9 +69,9 @@ __global__ __launch_bounds__(kBlock) void cdae_compact_rows_kernel(
       for (int k = 0; k < 4; ++k) {
         if (v[k] == 0.f) continue;
         const int64_t e = r * I + c + k;            // flat position: its Philox group and word
-        const uint4 w = cs_philox4x32_10(make_uint4((uint32_t)(e >> 2), (uint32_t)((e >> 2) >> 32), 0u, 0u), key);
+        const uint4 w = philox4x32<10>(make_uint4((uint32_t)(e >> 2), (uint32_t)((e >> 2) >> 32), 0u, 0u), key);
         const uint32_t word = (e & 3) == 0 ? w.x : (e & 3) == 1 ? w.y : (e & 3) == 2 ? w.z : w.w;
-        v[k] = cs_u01(word) >= p ? v[k] * scale : 0.0f;
+        v[k] = u01(word) >= p ? v[k] * scale : 0.0f;
       }
     }
     bool sel[4];
@@ -111,12 +97,12 @@ __global__ __launch_bounds__(kBlock) void cdae_compact_rows_kernel(
     lbase += tot >> 16;
   }
   if (lane == 0) {
-    count[r * kParts + part] = base;
-    if (PAIR) lcount[r * kParts + part] = lbase;
+    count[r * kListParts + part] = base;
+    if (PAIR) lcount[r * kListParts + part] = lbase;
   }
 }
 
-// The (column, value) list of one row, gathered from its kParts sub-lists into LDS in column order, kListCap
+// The (column, value) list of one row, gathered from its kListParts sub-lists into LDS in column order, kListCap
 // entries at a time.
 constexpr int kListCap = 2048;
 
@@ -127,19 +113,19 @@ __device__ __forceinline__ int gather_row_list(const int32_t* __restrict__ cols,
   // starting at overall entry `skip`
   if (threadIdx.x == 0) {
     int acc = 0;
-    for (int q = 0; q < kParts; ++q) { s_pre[q] = acc; acc += count[r * kParts + q]; }
-    s_pre[kParts] = acc;
+    for (int q = 0; q < kListParts; ++q) { s_pre[q] = acc; acc += count[r * kListParts + q]; }
+    s_pre[kListParts] = acc;
   }
   __syncthreads();
-  const int total = s_pre[kParts];
+  const int total = s_pre[kListParts];
   const int n = min(kListCap, total - skip);
   for (int i = threadIdx.x; i < n; i += kBlock) {
     const int e = skip + i;
     int q = 0;
 #pragma unroll
-    for (int s = kParts / 2; s >= 1; s >>= 1)
+    for (int s = kListParts / 2; s >= 1; s >>= 1)
       if (s_pre[q + s] <= e) q += s;
-    const int64_t at = (r * kParts + q) * cpp + (e - s_pre[q]);
+    const int64_t at = (r * kListParts + q) * cpp + (e - s_pre[q]);
     s_col[i] = cols[at];
     s_val[i] = vals[at];
   }
@@ -157,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void cdae_sparse_encode_kernel(
     const float* __restrict__ Wh, const float* __restrict__ bh, const float* __restrict__ V,
     const int64_t* __restrict__ user, int64_t I, int H, int64_t num_users, int act, float* __restrict__ z,
     int32_t* __restrict__ err_flag) {
-  __shared__ int s_pre[kParts + 1];
+  __shared__ int s_pre[kListParts + 1];
   __shared__ int32_t s_col[kListCap];
   __shared__ float s_val[kListCap];
   const int64_t r = blockIdx.x;
@@ -180,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void cdae_sparse_encode_kernel(
         acc3 = fmaf(s_val[j + 3], wrow[s_col[j + 3] * pitch], acc3);
       }
       for (; j < n; ++j) acc0 = fmaf(s_val[j], wrow[s_col[j] * pitch], acc0);
-      const bool more = skip + n < s_pre[kParts];
+      const bool more = skip + n < s_pre[kListParts];
       __syncthreads();                               // the staged list is overwritten by the next round
       if (!more) break;
     }
@@ -203,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void cdae_sparse_dwh_accumulate_kernel(
     const int32_t* __restrict__ cols, const float* __restrict__ vals, const int32_t* __restrict__ count, int64_t cpp,
     const float* __restrict__ dz, int H, float* __restrict__ T, int32_t* __restrict__ claim, int32_t epoch,
     int32_t* __restrict__ touched, int32_t* __restrict__ n_touched) {
-  __shared__ int s_pre[kParts + 1];
+  __shared__ int s_pre[kListParts + 1];
   __shared__ int32_t s_col[kListCap];
   __shared__ float s_val[kListCap];
   const int64_t r = blockIdx.x;
@@ -215,7 +201,7 @@ __global__ __launch_bounds__(kBlock) void cdae_sparse_dwh_accumulate_kernel(
       const float g = dz[r * H + h];
       for (int j = 0; j < n; ++j) atomicAdd(T + (int64_t)s_col[j] * H + h, g * s_val[j]);
     }
-    const bool more = skip + n < s_pre[kParts];
+    const bool more = skip + n < s_pre[kListParts];
     __syncthreads();
     if (!more) break;
   }
@@ -243,7 +229,7 @@ __global__ __launch_bounds__(kBlock) void cdae_sparse_dwh_scatter_kernel(const i
 __global__ __launch_bounds__(kBlock) void cdae_sparse_dwh_t_kernel(
     const int32_t* __restrict__ cols, const float* __restrict__ vals, const int32_t* __restrict__ count, int64_t cpp,
     const float* __restrict__ dz, int H, float* __restrict__ dWhT, uint8_t* __restrict__ touched_items) {
-  __shared__ int s_pre[kParts + 1];
+  __shared__ int s_pre[kListParts + 1];
   __shared__ int32_t s_col[kListCap];
   __shared__ float s_val[kListCap];
   const int64_t r = blockIdx.x;
@@ -254,7 +240,7 @@ __global__ __launch_bounds__(kBlock) void cdae_sparse_dwh_t_kernel(
       const float g = dz[r * H + h];
       for (int j = 0; j < n; ++j) atomicAdd(dWhT + (int64_t)s_col[j] * H + h, g * s_val[j]);
     }
-    const bool more = skip + n < s_pre[kParts];
+    const bool more = skip + n < s_pre[kListParts];
     __syncthreads();
     if (!more) break;
   }
@@ -276,7 +262,7 @@ __global__ __launch_bounds__(kBlock) void cdae_hidden_bwd_dwh_t_kernel(
     float* __restrict__ dV, uint8_t* __restrict__ touched_users, float* __restrict__ dbh, float* __restrict__ dWhT,
     uint8_t* __restrict__ touched_items, const float* __restrict__ partial_loss, int64_t n_partials,
     float* __restrict__ stats, double* __restrict__ loss_accum) {
-  __shared__ int s_pre[kParts + 1];
+  __shared__ int s_pre[kListParts + 1];
   __shared__ int32_t s_col[kListCap];
   __shared__ float s_val[kListCap];
   __shared__ float s_red[kWavesPerBlock];
@@ -322,7 +308,7 @@ __global__ __launch_bounds__(kBlock) void cdae_hidden_bwd_dwh_t_kernel(
         for (int j = 0; j < n; ++j) atomicAdd(dWhT + (int64_t)s_col[j] * H + h0, g0[q] * s_val[j]);
       if (h1 < H)
         for (int j = 0; j < n; ++j) atomicAdd(dWhT + (int64_t)s_col[j] * H + h1, g1[q] * s_val[j]);
-      const bool more = skip + n < s_pre[kParts];
+      const bool more = skip + n < s_pre[kListParts];
       __syncthreads();
       if (!more) break;
     }
@@ -373,7 +359,7 @@ __global__ __launch_bounds__(kBlock) void cdae_sampled_decode_kernel(
     int64_t cpp, const float* __restrict__ z, const float* __restrict__ Wo, const float* __restrict__ bo, int H,
     int act, int splits, float* __restrict__ dz, float* __restrict__ dWo, float* __restrict__ dbo,
     float* __restrict__ partial_loss, int32_t* __restrict__ count) {
-  __shared__ int s_pre[kParts + 1];
+  __shared__ int s_pre[kListParts + 1];
   __shared__ int32_t s_col[kListCap];
   __shared__ float s_val[kListCap];
   __shared__ float s_dz[kHalves][kHalf * NK];
@@ -490,7 +476,7 @@ __global__ __launch_bounds__(kBlock) void cdae_sampled_decode_kernel(
         }
       }
     }
-    const bool more = skip + n < s_pre[kParts];
+    const bool more = skip + n < s_pre[kListParts];
     __syncthreads();
     if (!more) break;
   }
@@ -535,7 +521,7 @@ __global__ __launch_bounds__(kBlock) void cdae_loss_finalize_kernel(const float*
 }
 
 // The validation loss of SEVERAL batches scored by one yr_cdae_sampled_decode launch: workgroup q sums the loss
-// partials and the position counts (loss_count, kParts per row) of the rows of batch q -> mean_q; the last
+// partials and the position counts (loss_count, kListParts per row) of the rows of batch q -> mean_q; the last
 // workgroup to arrive adds the means in batch order (fixed order) to *loss_accum.  `arrive` is zero on entry and is
 // left zero.
 __global__ __launch_bounds__(kBlock) void cdae_loss_finalize_batched_kernel(
@@ -548,7 +534,7 @@ __global__ __launch_bounds__(kBlock) void cdae_loss_finalize_batched_kernel(
   float s = 0.0f;
   for (int64_t k = r0 * splits + threadIdx.x; k < r1 * splits; k += kBlock) s += partial_loss[k];
   int c = 0;
-  for (int64_t k = r0 * kParts + threadIdx.x; k < r1 * kParts; k += kBlock) c += loss_count[k];
+  for (int64_t k = r0 * kListParts + threadIdx.x; k < r1 * kListParts; k += kBlock) c += loss_count[k];
 #pragma unroll
   for (int d = kWave / 2; d >= 1; d >>= 1) c += __shfl_xor(c, d, kWave);
   if ((threadIdx.x & (kWave - 1)) == 0) s_cnt[threadIdx.x / kWave] = c;
@@ -589,7 +575,7 @@ extern "C" int yr_cdae_loss_finalize_batched(const float* partial_loss, int spli
 extern "C" int64_t yr_cdae_sparse_part_columns(int64_t I) {
   // columns per part: I / 32 rounded up to a multiple of 4
   if (I <= 0) return YR_ERR_BADARG;
-  return ((I + kParts - 1) / kParts + 3) / 4 * 4;
+  return ((I + kListParts - 1) / kListParts + 3) / 4 * 4;
 }
 
 extern "C" int yr_cdae_compact_rows(const float* x, int64_t B, int64_t I, uint64_t seed, double p, int32_t* cols,
@@ -598,7 +584,7 @@ extern "C" int yr_cdae_compact_rows(const float* x, int64_t B, int64_t I, uint64
   if (B == 0) return 0;
   if (!x || !cols || !vals || !count) return YR_ERR_BADARG;
   const int64_t cpp = yr_cdae_sparse_part_columns(I);
-  hipLaunchKernelGGL((cdae_compact_rows_kernel<false>), dim3((unsigned)B, kParts / kWavesPerBlock), dim3(kBlock), 0,
+  hipLaunchKernelGGL((cdae_compact_rows_kernel<false>), dim3((unsigned)B, kListParts / kWavesPerBlock), dim3(kBlock), 0,
                      (hipStream_t)stream, x, (const float*)nullptr, I, seed, (float)p, (float)(1.0 / (1.0 - p)), cpp,
                      cols, vals, count, (int32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr);
   return launch_status();
@@ -662,7 +648,7 @@ extern "C" int yr_cdae_compact_pair(const float* x, const float* negative_mask, 
     return YR_ERR_BADARG;
   const int64_t cpp = yr_cdae_sparse_part_columns(I);
   if (cpp >= 32768) return YR_ERR_UNSUPPORTED;           // the two prefix sums share one 32-bit scan
-  hipLaunchKernelGGL((cdae_compact_rows_kernel<true>), dim3((unsigned)B, kParts / kWavesPerBlock), dim3(kBlock), 0,
+  hipLaunchKernelGGL((cdae_compact_rows_kernel<true>), dim3((unsigned)B, kListParts / kWavesPerBlock), dim3(kBlock), 0,
                      (hipStream_t)stream, x, negative_mask, I, seed, (float)p, (float)(1.0 / (1.0 - p)), cpp, cols,
                      vals, count, loss_cols, loss_targets, loss_count);
   return launch_status();

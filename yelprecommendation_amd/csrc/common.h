@@ -11,6 +11,9 @@ constexpr int kWave = 64;
 constexpr int kBlock = 256;            // 4 waves, one per SIMD
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxGrid = YR_LOSS_PARTIALS;   // 256 CUs x 8 workgroups
+// CDAE (column, value) lists: a row's columns are cut into this many ranges, one sub-list each (csrc/cdae_sparse.hip
+// consumes the layout; csrc/cdae_lists.hip and yr_cdae_compact_rows produce it)
+constexpr int kListParts = 32;
 
 // Row geometry for an embedding width D: a row is spread over LPR lanes holding
 // EPL consecutive floats each, so one wave-instruction touches 64/LPR rows with
@@ -53,6 +56,17 @@ __device__ __forceinline__ float group_sum_dpp(float x) {
   if (LPR >= 32) x += __shfl_xor(x, 16, kWave);
   return x;
 }
+
+// 16 f32 accumulators of a 32x32 MFMA tile (v_mfma_f32_32x32x*), and 16-byte loads / stores of four floats
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+__device__ __forceinline__ f32x16 zero16() {
+  f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  return z;
+}
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
 // Fast transcendental forms (v_exp_f32 / v_log_f32 / v_rcp_f32, about 1 ulp each) for the
 // per-triplet sigmoid / softplus: the library expf/log1pf/IEEE divide cost ~10x the instructions.

@@ -20,7 +20,6 @@
 
 namespace yr {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int kDcnMaxF = 512;                 // 4 * D, D <= 128
 constexpr int kDcnMaxH = 1024;                // width of the last hidden layer

@@ -18,7 +18,6 @@
 
 namespace yr {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int kEvalUsers = 128;   // per workgroup
 constexpr int kEvalItems = 128;

@@ -28,15 +28,15 @@
 // chip at Yelp2018 size (one wave per 32 users alone is < 1 wave per SIMD); each slice keeps its own
 // top-k per user and a second small kernel merges the S sorted partial lists.  A PRESCAN launch (below)
 // gives all lists of a user a common starting threshold.
-// Order: score descending, item id ascending among equal scores (as csrc/topk.hip).
+// Order: score descending, item id ascending among equal scores (csrc/topk_order.h, shared with csrc/topk.hip).
 // Built with -mllvm -amdgpu-mfma-vgpr-form (csrc/Makefile): accumulators in VGPRs.
 #include <algorithm>
 
 #include "common.h"
+#include "topk_order.h"
 
 namespace yr {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 constexpr int kEtUsersPerWave = 32;
@@ -80,21 +80,12 @@ __device__ unsigned long long g_et_phase[8];
 #define ET_CLK() 0ll
 #endif
 
-struct TopEntry {
-  float s;
-  int32_t i;
-};
-
-__device__ __forceinline__ bool et_better(float s, int32_t i, float s2, int32_t i2) {
-  return s > s2 || (s == s2 && i < i2);
-}
-
 // insert (cs, ci) into the lane's sorted list where `live`; the displaced entries bubble down
 template <int KK>
 __device__ __forceinline__ void et_bubble(float (&Ls)[KK], int32_t (&Li)[KK], float cs, int32_t ci, bool live) {
 #pragma unroll
   for (int e = 0; e < KK; ++e) {
-    const bool sw = live && et_better(cs, ci, Ls[e], Li[e]);
+    const bool sw = live && better(cs, ci, Ls[e], Li[e]);
     const float ts = Ls[e];
     const int32_t ti = Li[e];
     Ls[e] = sw ? cs : ts;
@@ -1054,7 +1045,7 @@ __global__ __launch_bounds__(kBlock) void mf_eval_merge_kernel(const TopEntry* _
       if (cur[s] >= k) continue;
       const TopEntry t = P[s * k + cur[s]];
       if (t.i == 0x7fffffff) continue;
-      if (best < 0 || et_better(t.s, t.i, bs, bi)) { best = s; bs = t.s; bi = t.i; }
+      if (best < 0 || better(t.s, t.i, bs, bi)) { best = s; bs = t.s; bi = t.i; }
     }
     if (best >= 0) {
 #pragma unroll

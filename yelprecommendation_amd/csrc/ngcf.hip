@@ -22,9 +22,7 @@
 
 namespace yr {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-__device__ __forceinline__ float4 ngcf_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 // --------------------------------------------------------------------------- SpMM
 constexpr int kSpmmUnroll = 8;
@@ -52,7 +50,7 @@ __device__ __forceinline__ void spmm_accumulate(const int32_t* __restrict__ col,
 #pragma unroll
     for (int q = 0; q < kSpmmUnroll; ++q) {
       wc[q] = w[q];
-      r[q] = c[q] >= 0 ? ngcf_ld4(Xl + (int64_t)c[q] * D) : make_float4(0.f, 0.f, 0.f, 0.f);
+      r[q] = c[q] >= 0 ? ld4(Xl + (int64_t)c[q] * D) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     const int nbase = base + step * kSpmmUnroll;
 #pragma unroll
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(const int32_t* __restr
         }
         float* dst = Y + (int64_t)row * D + 4 * l;
         if (ACCUM) {
-          const float4 old = ngcf_ld4(dst);
+          const float4 old = ld4(dst);
           t.x += old.x; t.y += old.y; t.z += old.z; t.w += old.w;
         }
         *reinterpret_cast<float4*>(dst) = t;
@@ -136,7 +134,7 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(const int32_t* __restr
       if (grp == 0) {
         float* dst = Y + (int64_t)row * D + 4 * l;
         if (ACCUM) {
-          const float4 old = ngcf_ld4(dst);
+          const float4 old = ld4(dst);
           acc.x += old.x; acc.y += old.y; acc.z += old.z; acc.w += old.w;
         }
         *reinterpret_cast<float4*>(dst) = acc;
@@ -192,7 +190,7 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_sliced_kernel(const int32_t* 
       if (grp == 0) {
         float* dst = Y + (int64_t)row * D + out_off;
         if (ACCUM) {
-          const float4 old = ngcf_ld4(dst);
+          const float4 old = ld4(dst);
           acc.x += old.x; acc.y += old.y; acc.z += old.z; acc.w += old.w;
         }
         *reinterpret_cast<float4*>(dst) = acc;
@@ -242,9 +240,9 @@ __global__ __launch_bounds__(kBlock) void ngcf_score_kernel(LayerPtrs L, int n_l
 #pragma unroll 4
       for (int k = 0; k < n_layers; ++k) {
         const float* E = L.p[k];
-        const float4 ru = ngcf_ld4(E + ou), rp = ngcf_ld4(E + op);
+        const float4 ru = ld4(E + ou), rp = ld4(E + op);
         sp += dot4(ru, rp);
-        if (NEG) sn += dot4(ru, ngcf_ld4(E + on));
+        if (NEG) sn += dot4(ru, ld4(E + on));
       }
     }
     sp = group_sum<LPR>(sp);
@@ -310,11 +308,6 @@ __global__ __launch_bounds__(kBlock) void ngcf_score_bwd_kernel(LayerPtrs L, Lay
 // k-slots of each v_mfma_f32_32x32x2_f32 step are mapped to the two halves of the K range.
 // Output: col = lane & 31, row = (reg & 3) + 8*(reg >> 2) + 4*(lane >> 5).
 constexpr float kSlope = 0.01f;   // nn.functional.leaky_relu default (models/ngcf.py:72)
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  return z;
-}
 
 // The 32-row operand tiles are fetched with coalesced 16-byte loads (whole rows per lane group) and
 // handed to the MFMA register layout through a wave-private LDS tile (pitch D+4: conflict-free
@@ -382,8 +375,8 @@ __global__ __launch_bounds__(kWave) void ngcf_dense_fwd_kernel(const float* __re
       float4 e = make_float4(0.f, 0.f, 0.f, 0.f), z = e;
       const int64_t pr = dense_row<D, SUB>(rows, row0 + r, cnt);
       if (pr >= 0) {
-        e = ngcf_ld4(E + pr * D + c4);
-        z = ngcf_ld4(Z + pr * D + c4);
+        e = ld4(E + pr * D + c4);
+        z = ld4(Z + pr * D + c4);
       }
       *reinterpret_cast<float4*>(s_a + r * T::PITCH + c4) = make_float4(z.x + e.x, z.y + e.y, z.z + e.z, z.w + e.w);
       *reinterpret_cast<float4*>(s_h + r * T::PITCH + c4) = make_float4(e.x * z.x, e.y * z.y, e.z * z.z, e.w * z.w);
@@ -405,14 +398,14 @@ __global__ __launch_bounds__(kWave) void ngcf_dense_fwd_kernel(const float* __re
     float b[HALF];
 #pragma unroll
     for (int q = 0; q < HALF / 4; ++q) {
-      const float4 w = j < D ? ngcf_ld4(W1 + j * D + h * HALF + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 w = j < D ? ld4(W1 + j * D + h * HALF + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
       b[4 * q + 0] = w.x; b[4 * q + 1] = w.y; b[4 * q + 2] = w.z; b[4 * q + 3] = w.w;
     }
 #pragma unroll
     for (int s = 0; s < HALF; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b[s], aA[s], acc, 0, 0, 0);
 #pragma unroll
     for (int q = 0; q < HALF / 4; ++q) {
-      const float4 w = j < D ? ngcf_ld4(W2 + j * D + h * HALF + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 w = j < D ? ld4(W2 + j * D + h * HALF + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
       b[4 * q + 0] = w.x; b[4 * q + 1] = w.y; b[4 * q + 2] = w.z; b[4 * q + 3] = w.w;
     }
 #pragma unroll
@@ -466,8 +459,8 @@ __global__ __launch_bounds__(kWave) void ngcf_dense_bwd_data_kernel(
       float4 g = make_float4(0.f, 0.f, 0.f, 0.f), o = g;
       const int64_t pr = dense_row<D, SUB>(rows, row0 + r, cnt);
       if (pr >= 0) {
-        g = ngcf_ld4(dEout + pr * D + c4);
-        o = ngcf_ld4(Eout + pr * D + c4);
+        g = ld4(dEout + pr * D + c4);
+        o = ld4(Eout + pr * D + c4);
       }
       *reinterpret_cast<float4*>(s_p + r * T::PITCH + c4) =
           make_float4(o.x > 0.0f ? g.x : kSlope * g.x, o.y > 0.0f ? g.y : kSlope * g.y,
@@ -488,14 +481,14 @@ __global__ __launch_bounds__(kWave) void ngcf_dense_bwd_data_kernel(
     float b[HALF];
 #pragma unroll
     for (int q = 0; q < HALF / 4; ++q) {
-      const float4 w = c < D ? ngcf_ld4(W1T + c * D + h * HALF + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 w = c < D ? ld4(W1T + c * D + h * HALF + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
       b[4 * q + 0] = w.x; b[4 * q + 1] = w.y; b[4 * q + 2] = w.z; b[4 * q + 3] = w.w;
     }
 #pragma unroll
     for (int s = 0; s < HALF; ++s) accA = __builtin_amdgcn_mfma_f32_32x32x2f32(b[s], a[s], accA, 0, 0, 0);
 #pragma unroll
     for (int q = 0; q < HALF / 4; ++q) {
-      const float4 w = c < D ? ngcf_ld4(W2T + c * D + h * HALF + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 w = c < D ? ld4(W2T + c * D + h * HALF + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
       b[4 * q + 0] = w.x; b[4 * q + 1] = w.y; b[4 * q + 2] = w.z; b[4 * q + 3] = w.w;
     }
 #pragma unroll
@@ -508,7 +501,7 @@ __global__ __launch_bounds__(kWave) void ngcf_dense_bwd_data_kernel(
         const int cc = t * 32 + 8 * g + 4 * h;
         if (cc < D) {
           const int64_t o = out_row * D + cc;
-          const float4 e = ngcf_ld4(E + o), z = ngcf_ld4(Z + o);
+          const float4 e = ld4(E + o), z = ld4(Z + o);
           float4 de = *reinterpret_cast<const float4*>(dE + o);
           float4 dz;
           dz.x = accA[4 * g + 0] + accH[4 * g + 0] * e.x;
@@ -571,7 +564,7 @@ __global__ __launch_bounds__(kBlock) void ngcf_dense_bwd_weight_kernel(
       pg[v] = po[v] = pe[v] = pz[v] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (r < n) {
         const int64_t o = (SUB ? (int64_t)rows[r] : r) * D + c4;
-        pg[v] = ngcf_ld4(dEout + o); po[v] = ngcf_ld4(Eout + o); pe[v] = ngcf_ld4(E + o); pz[v] = ngcf_ld4(Z + o);
+        pg[v] = ld4(dEout + o); po[v] = ld4(Eout + o); pe[v] = ld4(E + o); pz[v] = ld4(Z + o);
       }
     }
   };

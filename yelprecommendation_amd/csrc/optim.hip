@@ -5,25 +5,10 @@
 // every row moves every step — a lazy/sparse update would NOT be equivalent).
 // Formula = torch/optim/adam.py::_single_tensor_adam (see oracle/adam.py).
 // Pure HBM-bound elementwise work: read p,g,m,v, write p,m,v (+ g = 0).
+#include "adam.h"
 #include "common.h"
 
 namespace yr {
-
-struct AdamScalars {
-  float decay_mul, neg_step, bc2_sqrt, one_m_b1, beta2, one_m_b2, eps, wd;
-};
-
-template <bool DECOUPLED>
-__device__ __forceinline__ void adam_element(float& p, float grad, float& m, float& v, const AdamScalars& c) {
-  if (c.wd != 0.0f) {
-    if (DECOUPLED) p *= c.decay_mul;
-    else grad = grad + c.wd * p;
-  }
-  m = m + c.one_m_b1 * (grad - m);               // lerp_
-  v = v * c.beta2 + (c.one_m_b2 * grad) * grad;   // mul_, addcmul_
-  const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
-  p = p + (c.neg_step * m) / denom;               // addcdiv_
-}
 
 // main body: 16 bytes per lane; elements [4*n4, n) are the scalar tail of block 0
 template <bool DECOUPLED, bool ZERO_GRAD>
@@ -37,10 +22,10 @@ __global__ __launch_bounds__(kBlock) void adam_dense_kernel(float* __restrict__ 
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += stride) {
     float4 P = p4[i], G = g4[i], M = m4[i], V = v4[i];
-    adam_element<DECOUPLED>(P.x, G.x, M.x, V.x, c);
-    adam_element<DECOUPLED>(P.y, G.y, M.y, V.y, c);
-    adam_element<DECOUPLED>(P.z, G.z, M.z, V.z, c);
-    adam_element<DECOUPLED>(P.w, G.w, M.w, V.w, c);
+    adam_element(P.x, G.x, M.x, V.x, c, std::bool_constant<DECOUPLED>());
+    adam_element(P.y, G.y, M.y, V.y, c, std::bool_constant<DECOUPLED>());
+    adam_element(P.z, G.z, M.z, V.z, c, std::bool_constant<DECOUPLED>());
+    adam_element(P.w, G.w, M.w, V.w, c, std::bool_constant<DECOUPLED>());
     p4[i] = P;
     m4[i] = M;
     v4[i] = V;
@@ -49,7 +34,7 @@ __global__ __launch_bounds__(kBlock) void adam_dense_kernel(float* __restrict__ 
   if (blockIdx.x == 0) {
     const int64_t i = 4 * n4 + threadIdx.x;
     if (i < n) {
-      adam_element<DECOUPLED>(p[i], g[i], m[i], v[i], c);
+      adam_element(p[i], g[i], m[i], v[i], c, std::bool_constant<DECOUPLED>());
       if (ZERO_GRAD) g[i] = 0.0f;
     }
   }
@@ -73,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void adam_dense_multi_kernel(AdamMulti t, A
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     float P = p[i], G = g[i], M = m[i], V = v[i];
-    adam_element<DECOUPLED>(P, G, M, V, c);
+    adam_element(P, G, M, V, c, std::bool_constant<DECOUPLED>());
     p[i] = P; m[i] = M; v[i] = V;
     if (ZERO_GRAD) g[i] = 0.0f;
   }
@@ -114,10 +99,10 @@ __global__ __launch_bounds__(kBlock) void adam_dual_kernel(DualAdam t, AdamScala
       gp[j] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (tp && j % t.row4 == 0) tp[row] = 0;     // after every lane of the row (same wave) has read the mark
     }
-    adam_element<DECOUPLED>(P.x, G.x, M.x, V.x, c);
-    adam_element<DECOUPLED>(P.y, G.y, M.y, V.y, c);
-    adam_element<DECOUPLED>(P.z, G.z, M.z, V.z, c);
-    adam_element<DECOUPLED>(P.w, G.w, M.w, V.w, c);
+    adam_element(P.x, G.x, M.x, V.x, c, std::bool_constant<DECOUPLED>());
+    adam_element(P.y, G.y, M.y, V.y, c, std::bool_constant<DECOUPLED>());
+    adam_element(P.z, G.z, M.z, V.z, c, std::bool_constant<DECOUPLED>());
+    adam_element(P.w, G.w, M.w, V.w, c, std::bool_constant<DECOUPLED>());
     pp[j] = P;
     mp[j] = M;
     vp[j] = V;
@@ -182,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void adam_flat_kernel(AdamFlat t, AdamScala
         float* v = reinterpret_cast<float*>(t.v[k] + j);
         const float gs = t.scaled[k] ? inv_count : 1.0f;
         for (int e = 0; e < t.tail[k]; ++e) {
-          adam_element<DECOUPLED>(p[e], g[e] * gs, m[e], v[e], c);
+          adam_element(p[e], g[e] * gs, m[e], v[e], c, std::bool_constant<DECOUPLED>());
           if (t.clear[k]) g[e] = 0.0f;
         }
       }
@@ -203,10 +188,10 @@ __global__ __launch_bounds__(kBlock) void adam_flat_kernel(AdamFlat t, AdamScala
       if (tp && (j & ((1 << shift) - 1)) == 0) tp[row] = 0;   // after every lane of the row (same wave) has read the mark
     }
     if (t.scaled[k]) { G.x *= inv_count; G.y *= inv_count; G.z *= inv_count; G.w *= inv_count; }
-    adam_element<DECOUPLED>(P.x, G.x, M.x, V.x, c);
-    adam_element<DECOUPLED>(P.y, G.y, M.y, V.y, c);
-    adam_element<DECOUPLED>(P.z, G.z, M.z, V.z, c);
-    adam_element<DECOUPLED>(P.w, G.w, M.w, V.w, c);
+    adam_element(P.x, G.x, M.x, V.x, c, std::bool_constant<DECOUPLED>());
+    adam_element(P.y, G.y, M.y, V.y, c, std::bool_constant<DECOUPLED>());
+    adam_element(P.z, G.z, M.z, V.z, c, std::bool_constant<DECOUPLED>());
+    adam_element(P.w, G.w, M.w, V.w, c, std::bool_constant<DECOUPLED>());
     t.p[k][j] = P;
     t.m[k][j] = M;
     t.v[k][j] = V;
@@ -262,15 +247,7 @@ extern "C" int yr_adam_dense(float* p, float* g, float* m, float* v, int64_t n, 
   const int64_t n4 = n / 4;
   const int grid = grid_for(n4 > 0 ? n4 : 1, kBlock);
   hipStream_t s = (hipStream_t)stream;
-  AdamScalars c;
-  c.decay_mul = (float)(1.0 - lr * weight_decay);
-  c.neg_step = (float)(-step_size);
-  c.bc2_sqrt = (float)bc2_sqrt;
-  c.one_m_b1 = (float)(1.0 - beta1);
-  c.beta2 = (float)beta2;
-  c.one_m_b2 = (float)(1.0 - beta2);
-  c.eps = (float)eps;
-  c.wd = (float)weight_decay;
+  const AdamScalars c = adam_scalars(lr, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay);
 #define YR_LAUNCH_ADAM(DEC, ZG) \
   hipLaunchKernelGGL((adam_dense_kernel<DEC, ZG>), dim3(grid), dim3(kBlock), 0, s, p, g, m, v, n4, n, c)
   if (mode == YR_OPT_ADAMW) {
@@ -305,15 +282,7 @@ extern "C" int yr_adam_dense_dual(float* p0, float* g0, float* m0, float* v0, in
   t.touched0 = touched0; t.touched1 = touched1;
   t.n4_0 = n0 / 4; t.n4_1 = n1 / 4;
   t.row4 = row_width > 0 ? row_width / 4 : 1;
-  AdamScalars c;
-  c.decay_mul = (float)(1.0 - lr * weight_decay);
-  c.neg_step = (float)(-step_size);
-  c.bc2_sqrt = (float)bc2_sqrt;
-  c.one_m_b1 = (float)(1.0 - beta1);
-  c.beta2 = (float)beta2;
-  c.one_m_b2 = (float)(1.0 - beta2);
-  c.eps = (float)eps;
-  c.wd = (float)weight_decay;
+  const AdamScalars c = adam_scalars(lr, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay);
   const int64_t total = t.n4_0 + t.n4_1;
   const int grid = grid_for(total > 0 ? total : 1, kBlock);
   hipStream_t s = (hipStream_t)stream;
@@ -342,15 +311,7 @@ extern "C" int yr_adam_dense_multi(float* const* p, float* const* g, float* cons
     if (n[k] > longest) longest = n[k];
   }
   if (longest == 0) return 0;
-  AdamScalars c;
-  c.decay_mul = (float)(1.0 - lr * weight_decay);
-  c.neg_step = (float)(-step_size);
-  c.bc2_sqrt = (float)bc2_sqrt;
-  c.one_m_b1 = (float)(1.0 - beta1);
-  c.beta2 = (float)beta2;
-  c.one_m_b2 = (float)(1.0 - beta2);
-  c.eps = (float)eps;
-  c.wd = (float)weight_decay;
+  const AdamScalars c = adam_scalars(lr, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay);
   int gx = grid_for(longest, kBlock);
   if (gx > 1024) gx = 1024;
   const dim3 grid((unsigned)gx, (unsigned)count);
@@ -402,15 +363,7 @@ extern "C" int yr_adam_dense_flat(float* const* p, float* const* g, float* const
   if (used == 0) return 0;
   t.count = used;
   t.grad_count = grad_count;
-  AdamScalars c;
-  c.decay_mul = (float)(1.0 - lr * weight_decay);
-  c.neg_step = (float)(-step_size);
-  c.bc2_sqrt = (float)bc2_sqrt;
-  c.one_m_b1 = (float)(1.0 - beta1);
-  c.beta2 = (float)beta2;
-  c.one_m_b2 = (float)(1.0 - beta2);
-  c.eps = (float)eps;
-  c.wd = (float)weight_decay;
+  const AdamScalars c = adam_scalars(lr, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay);
   const int grid = (int)(chunks < kMaxGrid ? chunks : kMaxGrid);
   hipStream_t s = (hipStream_t)stream;
   if (mode == YR_OPT_ADAMW) hipLaunchKernelGGL((adam_flat_kernel<true>), dim3(grid), dim3(kBlock), 0, s, t, c);

@@ -13,17 +13,9 @@
 // list heads emit the result in rank order.  Order: score descending, item id
 // ascending among equal scores (the reference's order among exact ties is unspecified).
 #include "common.h"
+#include "topk_order.h"
 
 namespace yr {
-
-struct Cand {
-  float s;
-  int32_t i;
-};
-
-__device__ __forceinline__ bool better(float s, int32_t i, float s2, int32_t i2) {
-  return s > s2 || (s == s2 && i < i2);
-}
 
 // kTkThreads threads per row: 1024 when there are few rows (a 256-row CDAE batch with 256 threads ran
 // one wave per SIMD, every element a fully exposed memory latency), 256 when the rows alone fill the chip

@@ -14,6 +14,7 @@
 //             not in the user's sorted avoid-list (binary search)
 // Integer work: the CPU statement oracle/triplet_sampler.py gives the same words bit for bit.
 #include "common.h"
+#include "philox.h"
 
 namespace yr {
 
@@ -34,18 +35,6 @@ __device__ __forceinline__ uint64_t feistel(uint64_t x, int half_bits, uint32_t 
     R = t;
   }
   return ((uint64_t)L << half_bits) | R;
-}
-
-__device__ __forceinline__ uint4 philox4x32_7(uint4 ctr, uint2 key) {
-#pragma unroll
-  for (int r = 0; r < 7; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += 0x9E3779B9u;
-    key.y += 0xBB67AE85u;
-  }
-  return ctr;
 }
 
 constexpr int kMaxDraws = 4096;   // after this many rejected draws the first free item >= the last draw is taken
@@ -77,7 +66,7 @@ __global__ __launch_bounds__(kBlock) void triplet_sample_kernel(
     const int64_t lo0 = avoid_ptr[u], hi0 = avoid_ptr[u + 1];
     for (int d = 0;; ++d) {
       // unbiased integer in [0, num_items): Lemire's multiply-shift with rejection of the short first interval
-      const uint4 w = philox4x32_7(make_uint4((uint32_t)t, (uint32_t)((uint64_t)t >> 32), (uint32_t)d, 0u), key);
+      const uint4 w = philox4x32<7>(make_uint4((uint32_t)t, (uint32_t)((uint64_t)t >> 32), (uint32_t)d, 0u), key);
       const uint32_t n32 = (uint32_t)num_items;
       uint64_t m = (uint64_t)w.x * n32;
       if ((uint32_t)m < n32) {

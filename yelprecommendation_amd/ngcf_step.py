@@ -14,7 +14,7 @@ import ctypes
 
 import torch
 
-from . import _lib, engine
+from . import _lib, engine, optim
 
 
 class NGCFStep:
@@ -34,11 +34,7 @@ class NGCFStep:
         f32 = torch.float32
         for p in self.params:                                                   # the optimizer's own Adam state
             engine._dev(p.data, f32, "parameter")
-            st = optimizer.state[p]
-            if not st:
-                st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            optim.adam_state(optimizer, p)
         arr = ctypes.c_void_p * len(self.params)
         self._p = arr(*[p.data.data_ptr() for p in self.params])
         self._m = arr(*[engine._dev(optimizer.state[p]["exp_avg"], f32, "exp_avg") for p in self.params])

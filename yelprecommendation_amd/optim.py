@@ -13,6 +13,17 @@ from torch.optim import Optimizer
 from . import engine
 
 
+def adam_state(optimizer, p):
+    """The Adam state of parameter ``p`` in ``optimizer.state``, created on first use exactly as ``Adam.step()`` does
+    (the fused steps update it themselves, before any ``step()`` has run)."""
+    st = optimizer.state[p]
+    if not st:
+        st["step"] = 0
+        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+    return st
+
+
 class _DenseBase(Optimizer):
     def _grad(self, p):
         g = p.grad
@@ -44,11 +55,7 @@ class Adam(_DenseBase):
                 g = self._grad(p)
                 if g is None:
                     continue
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st = adam_state(self, p)
                 st["step"] += 1
                 if p.numel() <= self.SMALL:
                     small.setdefault(st["step"], []).append((p.data, g, st["exp_avg"], st["exp_avg_sq"]))

@@ -84,11 +84,7 @@ class DCNTrainer(BaseTrainer):
         b1, b2 = group["betas"]
         tensors, step = [], None
         for p in group["params"]:
-            st = self.optimizer.state[p]
-            if not st:
-                st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st = optim.adam_state(self.optimizer, p)
             st["step"] += 1
             step = st["step"]
             tensors.append((p.data, p.grad, st["exp_avg"], st["exp_avg_sq"], None, 1))

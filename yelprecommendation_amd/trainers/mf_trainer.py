@@ -119,11 +119,7 @@ class MFTrainer(BaseTrainer):
         U, I = self.model.user_embedding.weight, self.model.item_embedding.weight
         group = self.optimizer.param_groups[0]
         for p in (U, I):
-            st = self.optimizer.state[p]
-            if not st:
-                st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            optim.adam_state(self.optimizer, p)
         sU, sI = self.optimizer.state[U], self.optimizer.state[I]
         lo, hi = self.shard.lo, self.shard.hi              # the whole table on one GPU
         # one step object for the whole run (its second user buffer, workspaces and partials are
