@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""Load balance of the owner passes' walk (csrc/bpr_pull.hip) for one batch of triplets, computed on the host.
+
+An owner workgroup sorts a bucket's records by row, chunk by chunk, and its four waves walk the sorted stream: a wave
+walks the light rows of the slots it finishes, GPW * unroll records per iteration; a heavy row (more than
+YR_HEAVY_ROW records in the chunk) is walked by all four waves together.  The workgroup lasts as long as its slowest
+wave.  For every bucket this prints the walk iterations of the slowest wave under three bindings of rows to waves:
+
+  index   wave w finishes rows [w RPW, (w + 1) RPW)                                   (the binding before rows were dealt)
+  dealt   rows by descending count of the bucket's first chunk, each to the least-loaded wave with a free slot,
+          ties by row / wave index; kept for the bucket's further chunks; a first chunk with fewer than
+          --deal-min * (R / 16)^2 records keeps the index order                         (deal_rows in bpr_pull.hip)
+  floor   the light records in four equal quarters
+
+and the records per bucket and per row.  The model takes a bucket's records in triplet order and cuts them every CAP
+records (the kernel takes them tile by tile, which is the same order up to the arrangement inside a tile).
+
+    python scripts/owner_walk_balance.py --bench [--batch 524288]     # step 0 of bench.py's batch pool (needs the GPU)
+    python scripts/owner_walk_balance.py --npz batch.npz --users N --items M   # arrays u, p, n
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def deal(counts, rpw, heavy_t):
+    """slot of every row (slot = wave * rpw + position): the rule of deal_rows"""
+    R = len(counts)
+    load = np.where(counts <= heavy_t, counts, 0)
+    order = sorted(range(R), key=lambda r: (-load[r], r))
+    wl, used, slot = [0] * 4, [0] * 4, [0] * R
+    for r in order:
+        w = min((w for w in range(4) if used[w] < rpw), key=lambda w: (wl[w], w))
+        slot[r] = w * rpw + used[w]
+        used[w] += 1
+        wl[w] += int(load[r])
+    return np.array(slot)
+
+
+def bucket_walk(rows, R, cap, heavy_t, per_iter, deal_min=0):
+    """rows: local row of every record of one bucket, in the order the owner meets them.
+    -> slowest-wave iterations (index, dealt, floor), mean-wave iterations (index, dealt)"""
+    rpw = R // 4
+    it = {"index": np.zeros(4), "dealt": np.zeros(4)}
+    floor = 0.0
+    slot = None
+    for c0 in range(0, len(rows), cap):
+        cnt = np.bincount(rows[c0:c0 + cap], minlength=R)
+        heavy = cnt > heavy_t
+        hv = sum(-(-int(c) // (4 * per_iter)) for c in cnt[heavy])
+        light = np.where(heavy, 0, cnt)
+        if slot is None:      # a first chunk below the bar keeps the identity (the deal's serial steps would not pay)
+            slot = deal(cnt, rpw, heavy_t) if cnt.sum() >= deal_min * R * R // 256 else np.arange(R)
+        for name, wave_of in (("index", np.arange(R) // rpw), ("dealt", slot // rpw)):
+            per_wave = np.bincount(wave_of, weights=light, minlength=4)
+            it[name] += np.ceil(per_wave / per_iter) + hv
+        floor += np.ceil(light.sum() / 4 / per_iter) + hv
+    return it["index"].max(), it["dealt"].max(), floor, it["index"].mean(), it["dealt"].mean()
+
+
+def side_table(name, row_ids, n_rows, R, cap, heavy_t, per_iter, out, deal_min=0):
+    """row_ids: the table row of every record, in triplet order"""
+    nb = (n_rows + R - 1) // R
+    order = np.argsort(row_ids // R, kind="stable")
+    srt = row_ids[order]
+    bounds = np.searchsorted(srt // R, np.arange(nb + 1))
+    res = np.array([bucket_walk(srt[bounds[k]:bounds[k + 1]] % R, R, cap, heavy_t, per_iter, deal_min) for k in range(nb)])
+    per_bucket = np.diff(bounds)
+    per_row = np.bincount(row_ids, minlength=n_rows)
+    pc = lambda a, q: float(np.percentile(a, q))
+    print(f"== {name} pass: {nb} buckets of {R} rows, {len(row_ids)} records, chunks of {cap}, heavy row > {heavy_t}, "
+          f"{per_iter} records per wave iteration", file=out)
+    print(f"records per bucket: mean {per_bucket.mean():.0f}  p50 {pc(per_bucket, 50):.0f}  p90 {pc(per_bucket, 90):.0f}  "
+          f"p99 {pc(per_bucket, 99):.0f}  max {per_bucket.max()}", file=out)
+    print(f"records per row:    mean {per_row.mean():.1f}  p50 {pc(per_row, 50):.0f}  p90 {pc(per_row, 90):.0f}  "
+          f"p99 {pc(per_row, 99):.0f}  max {per_row.max()}   rows over the heavy threshold: {(per_row > heavy_t).sum()}", file=out)
+    for tag, thr in (("> 800", 800), ("> 1024", 1024), ("> 2048", 2048)):
+        print(f"buckets with {tag} records: {(per_bucket > thr).sum()}", file=out)
+    print("slowest-wave walk iterations per bucket      mean    p50    p90    p99    max", file=out)
+    for j, tag in enumerate(("index order", "dealt", "floor (equal quarters)")):
+        a = res[:, j]
+        print(f"  {tag:40s} {a.mean():6.2f} {pc(a, 50):6.0f} {pc(a, 90):6.0f} {pc(a, 99):6.0f} {a.max():6.0f}", file=out)
+    busy = res[:, 3] > 0
+    print(f"slowest / mean wave, mean over buckets with records: index order {np.mean(res[busy, 0] / res[busy, 3]):.3f}   "
+          f"dealt {np.mean(res[busy, 1] / res[busy, 4]):.3f}", file=out)
+    print(f"dealt against index order: {100 * (res[:, 1].mean() / res[:, 0].mean() - 1):+.1f} %   "
+          f"floor: {100 * (res[:, 2].mean() / res[:, 0].mean() - 1):+.1f} %", file=out)
+    return res, per_bucket
+
+
+def bench_batch(batch):
+    """step 0 of bench.py's single-GPU batch pool"""
+    import torch
+    sys.path.insert(0, ROOT)
+    from yelprecommendation_amd.data.synthetic import YELP2018_ITEMS, YELP2018_USERS, make_interactions_torch
+    from yelprecommendation_amd.data.triplets import TripletSampler, split_train_rows
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(4321)
+    iu, ii = make_interactions_torch(YELP2018_USERS, YELP2018_ITEMS, 47.0, seed=1234, device=dev)
+    tr = split_train_rows(iu, ii, generator=gen) == 0
+    B = min(batch, int(tr.sum()))
+    su, sp, sn = TripletSampler(iu[tr], ii[tr], YELP2018_USERS, YELP2018_ITEMS, seed=99).stream(B * 4)
+    return (su[:B].cpu().numpy(), sp[:B].cpu().numpy(), sn[:B].cpu().numpy()), YELP2018_USERS, YELP2018_ITEMS
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--bench", action="store_true")
+    ap.add_argument("--batch", type=int, default=1 << 19)
+    ap.add_argument("--npz")
+    ap.add_argument("--users", type=int)
+    ap.add_argument("--items", type=int)
+    ap.add_argument("--dim", type=int, default=64)
+    ap.add_argument("--heavy-row", type=int, default=96)
+    ap.add_argument("--deal-min", type=int, default=256, help="YR_DEAL_MIN: first-chunk records (at 16-row buckets) from which rows are dealt")
+    ap.add_argument("--item-unroll", type=int, default=2)
+    ap.add_argument("--user-unroll", type=int, default=1)
+    args = ap.parse_args()
+    if args.bench:
+        (u, p, n), nu, ni = bench_batch(args.batch)
+    elif args.npz and args.users and args.items:
+        z = np.load(args.npz)
+        (u, p, n), nu, ni = (z["u"], z["p"], z["n"]), args.users, args.items
+    else:
+        ap.error("--bench, or --npz with --users and --items")
+    R = 1024 // args.dim
+    gpw = 64 // (args.dim // 4)
+    print(f"# batch of {len(u)} triplets, {nu} users x {ni} items, D = {args.dim}")
+    # item records in triplet order: the positive and the negative occurrence of every triplet
+    items = np.stack([p, n], 1).reshape(-1)
+    side_table("item", items, ni, R, 1024, args.heavy_row, gpw * args.item_unroll, sys.stdout, args.deal_min)
+    if (nu + R - 1) // R >= 768:      # below: one row per wave, nothing to deal
+        side_table("user", np.asarray(u), nu, R, 768, args.heavy_row, gpw * args.user_unroll, sys.stdout, args.deal_min)
+
+
+if __name__ == "__main__":
+    main()

@@ -24,15 +24,18 @@
 //        no partial lines shared between workgroups.
 //   2  owner_pass_kernel<USER>  the owner of bucket k reads segment k of every tile (offsets ->
 //        LDS prefix, flattened index -> (tile, position) by binary search), ranks the records by
-//        local row with LDS integer atomics and so gets ONE stream sorted by row in LDS.  Every wave
-//        walks a contiguous quarter of the stream, GPW records per step (one per lane group), several
+//        local row with LDS integer atomics and so gets ONE stream sorted by row in LDS.  A row is finished by one
+//        lane group of one wave (its SLOT, wave * RPW + group; a wave finishes RPW rows and keeps their running sums
+//        in registers).  Which slot takes which row is dealt by load once the first chunk's counts are known
+//        (deal_rows: longest row first to the least-loaded wave) and kept for the bucket; the stream is laid out in
+//        slot order and wave w walks the records of ITS slots, GPW records per step (one per lane group), several
 //        steps in flight: x_b = U[u].(I[p_b]-I[n_b]); loss += softplus(-x_b); g_b = -sigmoid(-x_b)/B;
-//        cur += g_b (I[p_b]-I[n_b]); coeff[b] = g_b (4 B per triplet for the item side).  When a
-//        lane group's row changes, the groups closing that row combine their sums with shuffles and
-//        add them to the wave's own slab of gradient rows in LDS (plain read-modify-write: no
-//        atomics anywhere).  Rows of any length are thereby spread over all waves; more than kCap
-//        records per bucket: further chunks into the same slabs.  Finally each lane group adds the
-//        four slabs of its row in fixed order and applies Adam: U_new[u] = Adam(U[u], acc).
+//        cur += g_b (I[p_b]-I[n_b]); coeff[b] = g_b (4 B per triplet for the item side).  When a lane group's row
+//        changes, the groups closing that row combine their sums with shuffles and the row's slot adds the result
+//        to its register total (no atomics anywhere).  A row with more than YR_HEAVY_ROW records in a chunk is
+//        walked by all four waves together, their partial sums meet in LDS in wave order.  More than kCap records
+//        per bucket: further chunks into the same totals.  Finally each lane group applies Adam to the row it was
+//        dealt: U_new[u] = Adam(U[u], acc).
 //   3  owner_pass_kernel<ITEM>  the same over the item buckets: {user, (+/-) coeff[b]} per
 //        occurrence, acc = sum g * U_old[user], I[i] = Adam(I[i], acc) (or the dense gradient rows
 //        for the multi-GPU all-reduce); workgroup 0 also reduces the loss partials of launch 2
@@ -42,8 +45,8 @@
 //
 // Layout: a row of D floats sits on LPR = D/4 lanes as float4 (16-byte loads/stores); a wave
 // works on GPW = 64/LPR contributions at once; the per-contribution dot product is a reduction
-// over LPR lanes only.  At the end a wave holds GPW consecutive rows, one per lane group: own row,
-// m, v and the Adam update stream 1 KB per wave instruction.
+// over LPR lanes only.  At the end a wave holds GPW rows of its bucket, one per lane group: own row,
+// m, v and the Adam update stream 256 B per lane group and instruction.
 #include "adam.h"
 #include "common.h"
 
@@ -86,6 +89,13 @@ constexpr int kMaxParts = 64;
 constexpr int kMaxTasks = 512;                   // helper workgroups at the front of the item pass's grid
 constexpr int kMaxSlots = 1024;                  // scratch slots of 1024 floats (one bucket's rows)
 constexpr int kBuildLanes = 4;                   // lanes that share one item bucket in the sizing workgroups of the USER pass
+#ifndef YR_DEAL
+#define YR_DEAL 1                     // 0: wave w finishes rows [w RPW, (w + 1) RPW) of its bucket (measurement only)
+#endif
+#ifndef YR_DEAL_MIN
+#define YR_DEAL_MIN 256
+#endif
+constexpr int kDealMin = YR_DEAL_MIN;            // records in a bucket's first chunk from which its rows are dealt (at R = 16)
 #ifndef YR_OWNER_WAVES
 #define YR_OWNER_WAVES 8              // waves per SIMD the owner pass is compiled for (8 workgroups per CU: <= 64 VGPRs)
 #endif
@@ -240,6 +250,7 @@ __global__ __launch_bounds__(kPartThreads) void tile_partition_kernel(
 
 #ifdef YR_STAMPS
 __device__ long long g_stamps[8192 * 8];
+__device__ int g_walk_iters[8192 * 4];           // walk iterations of each wave over the workgroup's first bucket
 #define YR_STAMP(i) do { if (threadIdx.x == 0 && first_bucket) g_stamps[(blockIdx.x + (USER ? 0 : 4096)) * 8 + (i)] = wall_clock64(); } while (0)
 #else
 #define YR_STAMP(i)
@@ -379,6 +390,41 @@ struct RowSums {
   __device__ __forceinline__ float4 finish(int) { return total; }
 };
 
+// Which lane group finishes which row.  A wave walks the records of the RPW rows it finishes, so a wave whose rows
+// are long keeps the workgroup alive while the others idle.  Once the first chunk's counts are known, wave 0 deals
+// the R local rows to the R slots (slot = wave * RPW + lane group): rows by descending light count (ties: lower row
+// first), each to the least-loaded wave that still has a free slot (ties: lower wave first).  Heavy rows are walked
+// by all waves and count as empty.  A pure function of the counts: the deterministic mode depends on that.
+// Lane w < 4 keeps wave w's key (load << 2 | w, INT_MAX once its slots are taken): scalar registers are scarce here.
+template <int R, int RPW>
+__device__ __forceinline__ void deal_rows(const int* s_cnt, unsigned char* s_slotof, unsigned char* s_rowof, int lane,
+                                          int heavy_t) {
+  static_assert(kWavesPerBlock == 4 && R == 4 * RPW, "four waves of RPW slots");
+  const int c = s_cnt[lane];
+  const int load = (lane < R && c <= heavy_t) ? c : 0;
+  // one key per row that orders them: longer rows first, equal rows by index (a single compare per pair: a separate
+  // `j < lane` is the same for every chunk, and the compiler keeps all R of them in scalar registers for the kernel's life)
+  const int order = (load << 6) | (kWave - 1 - lane);
+  int rank = 0;
+  for (int j = 0; j < R; ++j) rank += __builtin_amdgcn_readlane(order, j) > order ? 1 : 0;
+  int wkey = lane < kWavesPerBlock ? lane : 0x7fffffff, wused = 0;   // lane w < 4: wave w's key and slots taken
+  int slot = lane;                                // lanes past the bucket's rows keep the identity
+  for (int i = 0; i < R; ++i) {
+    const int src = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)__ballot(lane < R && rank == i)) - 1);
+    const int ci = __builtin_amdgcn_readlane(load, src);
+    const int w = min(min(__builtin_amdgcn_readlane(wkey, 0), __builtin_amdgcn_readlane(wkey, 1)),
+                      min(__builtin_amdgcn_readlane(wkey, 2), __builtin_amdgcn_readlane(wkey, 3))) & 3;
+    const int s = w * RPW + __builtin_amdgcn_readlane(wused, w);
+    if (lane == w) {
+      wused += 1;
+      wkey = wused == RPW ? 0x7fffffff : wkey + (ci << 2);
+    }
+    if (lane == src) slot = s;
+  }
+  s_slotof[lane] = (unsigned char)slot;
+  s_rowof[slot] = (unsigned char)lane;
+}
+
 #ifndef YR_USER_UNROLL
 #define YR_USER_UNROLL 1
 #endif
@@ -390,10 +436,12 @@ constexpr int kItemUnroll = YR_ITEM_UNROLL;
 constexpr int kTagShift = 10;    // s_idx entry = load-order index (< kCap) | local row << 10
 
 // One pass of a wave over the stream positions lo + first + k * stride < hi (sorted by row); books
-// row sums into `sums` (rows relative to `row_base`) or, with HEAVY, returns the sum of ONE row in `cur`.
-template <int D, bool USER, bool HEAVY>
+// row sums into `sums` (slots relative to `row_base`; LOOKUP: the entries are tagged with rows, whose slot is looked
+// up in s_slotof when the row closes; otherwise the tag is the slot) or, with HEAVY, returns the sum of ONE row in `cur`.
+template <int D, bool USER, bool HEAVY, bool LOOKUP>
 __device__ __forceinline__ void walk_stream(const OwnerArgs& a, const unsigned short* s_idx, const int* s_x,
-                                            const int* s_y, const int* s_z, const float4* s_own, int lo, int hi,
+                                            const int* s_y, const int* s_z, const float4* s_own,
+                                            const unsigned char* s_slotof, int lo, int hi,
                                             int first, int stride, int row_base, int grp, int l,
                                             RowSums<PullGeom<D>::LPR, PullGeom<D>::GPW>& sums, float4& cur,
                                             float& loss) {
@@ -428,7 +476,8 @@ __device__ __forceinline__ void walk_stream(const OwnerArgs& a, const unsigned s
       if (!HEAVY) {
         const bool closing = valid[q] && cur_row >= 0 && tag[q] != cur_row;
         if (__ballot(closing)) {
-          sums.book(closing, cur_row - row_base, cur, grp);
+          const int slot = LOOKUP ? (int)s_slotof[max(cur_row, 0)] : cur_row;
+          sums.book(closing, slot - row_base, cur, grp);
           if (closing) cur = zero4();
         }
         if (valid[q]) cur_row = tag[q];
@@ -458,7 +507,10 @@ __device__ __forceinline__ void walk_stream(const OwnerArgs& a, const unsigned s
       }
     }
   }
-  if (!HEAVY) sums.book(cur_row >= 0, cur_row - row_base, cur, grp);
+  if (!HEAVY) {
+    const int slot = LOOKUP ? (int)s_slotof[max(cur_row, 0)] : cur_row;
+    sums.book(cur_row >= 0, slot - row_base, cur, grp);
+  }
 }
 
 template <int D, bool USER, bool FUSE_ADAM, bool DET, int RPWX = 0>
@@ -468,13 +520,23 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
   constexpr int RPW = RPWX ? RPWX : GPW;         // rows a wave owns (RPWX = 0: one per lane group)
   static_assert(RPW <= GPW, "a wave finishes at most one row per lane group");
   constexpr int R = kWavesPerBlock * RPW;        // rows per bucket
+  constexpr int DEAL_BAR = kDealMin * (kWavesPerBlock * GPW) * (kWavesPerBlock * GPW) / 256;   // records in the first chunk
+  // rows dealt to the lane groups by load: not with one row per wave (nothing to deal), and not where a chunk can never
+  // hold DEAL_BAR records (D = 16, the user side at D = 32): those forms compile to the index-order binding
+  constexpr bool DEAL = RPWX == 0 && YR_DEAL && DEAL_BAR <= (USER ? kUserCap : kCap);
+  // The tag of a stream entry names what the walk needs without a further lookup.  Item pass: the SLOT (the walk only
+  // books sums, as it did before rows were dealt: it has no register to spare).  User pass: the local ROW (every
+  // record reads the row's own embedding from s_own), and the slot is looked up when a row closes.
+  constexpr bool TAG_SLOT = DEAL && !USER, LOOKUP = DEAL && USER;
   constexpr int CAP = USER ? kUserCap : kCap;    // records per chunk
   constexpr int PT = CAP / kBlock;
   __shared__ int s_pre[kTileGroup + 1];          // flattened start of every tile's segment
   __shared__ int s_base[kTileGroup];             // where the segment sits in the record array
   __shared__ int s_cnt[kWave];                   // records per local row in this chunk
   __shared__ int s_start[kWave];                 // where a row's records start in the sorted stream
-  __shared__ int s_light[kWave + 1];             // the same for light rows only (heavy rows: empty range)
+  __shared__ int s_light[kWave + 1];             // light rows only, by SLOT: wave w walks [s_light[w RPW], s_light[(w + 1) RPW])
+  __shared__ unsigned char s_slotof[DEAL ? kWave : 1];   // local row -> slot (wave * RPW + lane group) that finishes it
+  __shared__ unsigned char s_rowof[DEAL ? kWave : 1];    // slot -> local row; both valid once the bucket is `bound`
   __shared__ int s_x[CAP];                       // user: pos     item: user            (load order)
   __shared__ int s_y[CAP];                       // user: neg     item: signed coefficient (float bits)
   __shared__ int s_z[(USER || DET) ? CAP : 1];   // triplet id (item pass: | sign bit, kept for the deterministic order only)
@@ -487,7 +549,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const int grp = lane / LPR, l = lane % LPR;
   const bool finisher = grp < RPW;                // lane groups that finish a row (all of them unless RPW < GPW)
-  const int row_l = wave * RPW + (finisher ? grp : 0);
+  const int row_l = wave * RPW + (finisher ? grp : 0);   // this lane group's slot (= its row until the bucket is bound)
   float loss = 0.0f;
   __shared__ int s_last;
   if (USER && (int)blockIdx.x < a.build_blocks) {
@@ -502,6 +564,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
   const int owners = (int)gridDim.x - hb;
 #ifdef YR_STAMPS
   bool first_bucket = true;
+  int walk_iters = 0, heavy_iters = 0;
 #endif
   YR_STAMP(0);
 
@@ -524,9 +587,13 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
     // cost the item pass two VGPRs it does not have — 12 B of scratch per lane, caught by scripts/kernel_resources.py)
     const int t_begin = __builtin_amdgcn_readfirstlane(a.T * part / parts);
     const int t_end = __builtin_amdgcn_readfirstlane(a.T * (part + 1) / parts);
-    const int row_f = k * R + row_l;
-    const bool valid_f = finisher && row_f < a.rows;
-    const uint32_t o_f = (uint32_t)(row_f * D + 4 * l);
+    int row_t = row_l;                           // the local row this lane group finishes
+    int row_f = k * R + row_t;
+    bool valid_f = finisher && row_f < a.rows;
+    uint32_t o_f = (uint32_t)(row_f * D + 4 * l);
+    // DEAL: the binding of rows to slots is fixed by the first chunk that holds a record and kept for the bucket
+    // (the register totals persist over chunks, tile groups and windows); workgroup-uniform
+    bool bound = false;
     if (USER && finisher) s_own[row_l * LPR + l] = valid_f ? ld4o(a.own_old, o_f) : zero4();
     YR_STAMP(1);
     RowSums<LPR, GPW> sums;
@@ -687,21 +754,40 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
         __syncthreads();
         // sorted stream = light rows in row order, then the heavy rows (more than heavy_t records)
         if (wave == 0) {
-          const int c = s_cnt[lane];
+          if (DEAL && !bound) {
+            // the deal is R serial steps of wave 0 (about 1.4 us at R = 16) while the other waves wait, and a walk
+            // step takes 16 R records off the stream: a first chunk with few records (a short walk: nothing to win
+            // back) keeps the identity.  The bar grows with R * R — 64 records at D = 128, 256 at D = 64, a full item
+            // chunk at D = 32 (DEAL is off where no chunk can reach it)
+            if (n_rec >= DEAL_BAR) {
+              deal_rows<R, RPW>(s_cnt, s_slotof, s_rowof, lane, a.heavy_t);
+            } else {
+              s_slotof[lane] = (unsigned char)lane;
+              s_rowof[lane] = (unsigned char)lane;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+          }
+          // lane = slot: the stream is laid out in slot order
+          const int row = DEAL ? (int)s_rowof[lane] : lane;
+          const int c = s_cnt[row];
           const bool heavy = c > a.heavy_t;
           const int cl = heavy ? 0 : c, ch = heavy ? c : 0;
           const int il = wave_inclusive_scan(cl, lane), ih = wave_inclusive_scan(ch, lane);
           const int total_light = __shfl(il, kWave - 1, kWave);
           s_light[lane] = il - cl;
           if (lane == kWave - 1) s_light[kWave] = il;
-          s_start[lane] = heavy ? total_light + ih - ch : il - cl;
+          s_start[row] = heavy ? total_light + ih - ch : il - cl;
         }
+        bound = true;
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < PT; ++q)
-          if (key[q] >= 0)
-            s_idx[s_start[key[q] & 255] + (key[q] >> 8)] =
-                (unsigned short)((tid + q * kBlock) | ((key[q] & 255) << kTagShift));
+          if (key[q] >= 0) {
+            const int row = key[q] & 255;
+            const int tag = TAG_SLOT ? (int)s_slotof[row] : row;
+            s_idx[s_start[row] + (key[q] >> 8)] = (unsigned short)((tid + q * kBlock) | (tag << kTagShift));
+          }
         __syncthreads();
         if (DET) {
           // the ranks above came from LDS atomics in arrival order: re-rank every row by triplet id
@@ -714,7 +800,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
             at[q] = -1;
             if (pos < n_rec) {
               ent[q] = s_idx[pos];
-              const int r = ent[q] >> kTagShift;
+              const int r = TAG_SLOT ? (int)s_rowof[ent[q] >> kTagShift] : ent[q] >> kTagShift;
               const uint32_t mine = (uint32_t)s_z[ent[q] & ((1 << kTagShift) - 1)];
               const int lo = s_start[r], cnt = s_cnt[r];
               int before = 0;
@@ -729,11 +815,14 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
             if (at[q] >= 0) s_idx[at[q]] = ent[q];
           __syncthreads();
         }
-        // light rows: wave w walks the records of ITS rows [w GPW, (w+1) GPW), one per lane group and step
+        // light rows: wave w walks the records of ITS slots [w RPW, (w+1) RPW), one per lane group and step
         {
           float4 cur = zero4();
-          walk_stream<D, USER, false>(a, s_idx, s_x, s_y, s_z, s_own, s_light[wave * RPW], s_light[wave * RPW + RPW], grp,
-                                      GPW, wave * RPW, grp, l, sums, cur, loss);
+          walk_stream<D, USER, false, LOOKUP>(a, s_idx, s_x, s_y, s_z, s_own, s_slotof, s_light[wave * RPW],
+                                            s_light[wave * RPW + RPW], grp, GPW, wave * RPW, grp, l, sums, cur, loss);
+#ifdef YR_STAMPS
+          if (first_bucket) walk_iters += (s_light[wave * RPW + RPW] - s_light[wave * RPW] + GPW * (USER ? kUserUnroll : kItemUnroll) - 1) / (GPW * (USER ? kUserUnroll : kItemUnroll));
+#endif
         }
         // heavy rows of the chunk: all waves on one row, partial sums combined in wave order
         if (n_rec - s_light[kWave] > 0) {   // workgroup-uniform
@@ -743,12 +832,15 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
             if (cnt <= a.heavy_t) continue;       // workgroup-uniform
             const int lo = s_start[r];
             float4 t = zero4();
-            walk_stream<D, USER, true>(a, s_idx, s_x, s_y, s_z, s_own, lo, lo + cnt, wave * GPW + grp,
-                                       kWavesPerBlock * GPW, 0, grp, l, sums, t, loss);
+            walk_stream<D, USER, true, LOOKUP>(a, s_idx, s_x, s_y, s_z, s_own, s_slotof, lo, lo + cnt, wave * GPW + grp,
+                                             kWavesPerBlock * GPW, 0, grp, l, sums, t, loss);
+#ifdef YR_STAMPS
+            if (first_bucket) { walk_iters += (cnt + kWavesPerBlock * GPW * (USER ? kUserUnroll : kItemUnroll) - 1) / (kWavesPerBlock * GPW * (USER ? kUserUnroll : kItemUnroll)); heavy_iters += 1; }
+#endif
             cross_group_sum<LPR>(t);
             if (grp == 0) s_heavy[wave][l] = t;
             __syncthreads();
-            if (finisher && row_l == r) {
+            if (finisher && row_l == (DEAL ? (int)s_slotof[r] : r)) {
 #pragma unroll
               for (int w = 0; w < kWavesPerBlock; ++w) {
                 const float4 h = s_heavy[w][l];
@@ -764,6 +856,16 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
 
     YR_STAMP(3);
     float4 acc = sums.finish(grp);
+    if (DEAL) {                                  // the row this slot was dealt (a bucket without records: the identity)
+      if (bound) row_t = s_rowof[row_l];
+      row_f = k * R + row_t;
+      valid_f = row_f < a.rows;
+      // (the lane's column offset is taken afresh from the thread index, through an empty asm: otherwise 4 * l is kept
+      // over the whole walk for this one use — the register the D = 128 user pass then lacks went to scratch memory)
+      int t2 = tid;
+      asm volatile("" : "+v"(t2));
+      o_f = (uint32_t)(row_f * D + 4 * (t2 % LPR));
+    }
     if (!USER && parts > 1) {
       // a split bucket: leave this part's sums in its scratch slot; the last part to arrive adds the slots in part
       // order and goes on to the update, the others are done with the bucket
@@ -772,10 +874,15 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
       float* sbase = a.scratch;
       asm volatile("" : "+s"(sbase));
       float* slots = sbase + (int64_t)split_slot(a.split, a.nb)[k] * (R * D);
-      if (finisher) st4(slots + (int64_t)part * (R * D) + row_l * D + 4 * l, acc);
+      // slots are indexed by the TRUE local row: every part deals its own rows
+      if (finisher) st4(slots + (int64_t)part * (R * D) + row_t * D + 4 * l, acc);
       __threadfence();
       __syncthreads();
-      if (tid == 0) s_last = atomicAdd(split_arrive(a.split, a.nb) + k, 1) == parts - 1;
+      if (tid == 0) {
+        s_last = atomicAdd(split_arrive(a.split, a.nb) + k, 1) == parts - 1;
+        // every part has arrived: the counter starts clean for a further item pass over the same partition
+        if (s_last) split_arrive(a.split, a.nb)[k] = 0;
+      }
       __syncthreads();
       const bool last = s_last != 0;
       __syncthreads();                           // s_last may be rewritten by the next bucket
@@ -784,14 +891,14 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
       acc = zero4();
       if (finisher) {
         for (int q = 0; q < parts; ++q) {
-          const float4 t = ld4(slots + (int64_t)q * (R * D) + row_l * D + 4 * l);
+          const float4 t = ld4(slots + (int64_t)q * (R * D) + row_t * D + 4 * l);
           acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
         }
       }
     }
     if (valid_f) {
       if (FUSE_ADAM) {
-        float4 own = USER ? s_own[row_l * LPR + l] : ld4o(a.own_old, o_f);
+        float4 own = USER ? s_own[row_t * LPR + l] : ld4o(a.own_old, o_f);
         float4 M = ld4o(a.m, o_f), V = ld4o(a.v, o_f);
         adam_element(own.x, acc.x, M.x, V.x, a.adam.c, a.adam.decoupled);
         adam_element(own.y, acc.y, M.y, V.y, a.adam.c, a.adam.decoupled);
@@ -808,6 +915,13 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
     if (USER) __syncthreads();                   // s_own is rewritten for the next bucket
     YR_STAMP(5);
 #ifdef YR_STAMPS
+    if (first_bucket) {
+      if (lane == 0) g_walk_iters[(blockIdx.x + (USER ? 0 : 4096)) * 4 + wave] = walk_iters;
+      if (tid == 0) {                            // which bucket this was, and how many heavy-row walks it took
+        g_stamps[(blockIdx.x + (USER ? 0 : 4096)) * 8 + 6] = k;
+        g_stamps[(blockIdx.x + (USER ? 0 : 4096)) * 8 + 7] = heavy_iters;
+      }
+    }
     first_bucket = false;
 #endif
   }
@@ -912,6 +1026,9 @@ static int pull_check_common(int64_t B, int D, int64_t num_users, int64_t num_it
 #ifdef YR_STAMPS
 extern "C" int yr_debug_read_stamps(long long* host, int n) {
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(long long) * n);
+}
+extern "C" int yr_debug_read_walk_iters(int* host, int n) {
+  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_walk_iters), sizeof(int) * n);
 }
 #endif
 
