@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define YR_ENGINE_VERSION 29
+#define YR_ENGINE_VERSION 30
 
 #define YR_ERR_UNSUPPORTED (-1) /* embedding width / option not compiled in   */
 #define YR_ERR_BADARG      (-2) /* null pointer, negative size, misalignment  */
@@ -625,15 +625,7 @@ int yr_adam_dense(float *p, float *g, float *m, float *v, int64_t n,
                   double beta1, double beta2, double eps, double weight_decay,
                   int mode, int zero_grad, void *stream);
 
-/* Dense SGD (no momentum): p -= lr * (g + wd * p)   (base_trainer.py:39-40). */
-/* yr_adam_dense_multi: the same update for up to YR_ADAM_MULTI_MAX tensors in one launch (the small
- * weight matrices and biases beside an embedding table; all at the same step count).  p / g / m / v
- * / n are HOST arrays of `count` device pointers / element counts; no alignment requirement. */
 #define YR_ADAM_MULTI_MAX 16
-int yr_adam_dense_multi(float *const *p, float *const *g, float *const *m, float *const *v,
-                        const int64_t *n, int count, double lr, double step_size, double bc2_sqrt,
-                        double beta1, double beta2, double eps, double weight_decay, int mode,
-                        int zero_grad, void *stream);
 /* yr_adam_dense_flat: up to YR_ADAM_MULTI_MAX tensors of ANY size in one launch at 16 bytes per lane
  * (every buffer 16-byte aligned).  touched[k] (HOST array of device pointers,
  * entries may be NULL): one byte per row of row_width[k] floats (row_width / 4 a power of two <= 64) — the
@@ -644,6 +636,7 @@ int yr_adam_dense_flat(float *const *p, float *const *g, float *const *m, float 
                        const int64_t *n, uint8_t *const *touched, const int *row_width, const int *clear,
                        const int *scaled, const int32_t *grad_count, int count, double lr, double step_size, double bc2_sqrt, double beta1,
                        double beta2, double eps, double weight_decay, int mode, void *stream);
+/* Dense SGD (no momentum): p -= lr * (g + wd * p)   (base_trainer.py:39-40). */
 int yr_sgd_dense(float *p, float *g, int64_t n, double lr, double weight_decay,
                  int zero_grad, void *stream);
 

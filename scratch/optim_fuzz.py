@@ -20,7 +20,8 @@ for c in range(cases):
     multi = bool(rs.rand() < 0.5)
     kw = dict(beta1=b1, beta2=b2, eps=eps, weight_decay=wd, decoupled=dec)
     if multi:
-        engine.adam_dense_multi(devs, step, lr, zero_grad=True, **kw)
+        for s0 in range(0, len(devs), engine.ADAM_MULTI_MAX):
+            engine.adam_dense_flat([tup + (None, 1) for tup in devs[s0:s0 + engine.ADAM_MULTI_MAX]], step, lr, **kw)
     else:
         for tup in devs:
             if tup[0].numel(): engine.adam_dense(*tup, step, lr, zero_grad=True, **kw)

@@ -62,7 +62,7 @@ def main():
 
         def step():
             tr.model.bpr_loss_backward(u, p, n, loss_accum=tr._loss_accum)
-            tr._optimizer_step()
+            tr.optimizer.step(zero_grad=True)
         res[f"train_step_us_b{B}"] = round(_time(step, a.steps, a.warmup) * 1e6, 1)
     tr.model.check_indices()
 

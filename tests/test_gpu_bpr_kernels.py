@@ -110,15 +110,17 @@ def test_adam_dense(device, mode):
     np.testing.assert_allclose(dv.cpu().numpy(), v, rtol=1e-5, atol=1e-12)
 
 
+ADAM_SIZES = [1, 7, 64 * 64, 4099, 0, 128] + [33] * 14                      # 20 tensors > ADAM_MULTI_MAX
+
+
 @pytest.mark.parametrize("mode", ["adam", "adamw"])
-def test_adam_dense_multi_equals_single_launches(device, mode):
-    """yr_adam_dense_multi (one launch for the small tensors of a model) is bit-identical to one
+def test_adam_dense_flat_equals_single_launches(device, mode):
+    """yr_adam_dense_flat (one launch for up to ADAM_MULTI_MAX tensors of a model) is bit-identical to one
     yr_adam_dense per tensor: odd sizes, an empty tensor, more tensors than one launch takes."""
     from yelprecommendation_amd import engine
     rs = np.random.RandomState(3)
-    sizes = [1, 7, 64 * 64, 4099, 0, 128] + [33] * 14                       # 20 tensors > ADAM_MULTI_MAX
     mk = lambda n: torch.from_numpy(rs.standard_normal(n).astype(np.float32)).to(device)
-    A = [(mk(n), mk(n), mk(n).abs() * 0, mk(n).abs() * 0) for n in sizes]
+    A = [(mk(n), mk(n), mk(n).abs() * 0, mk(n).abs() * 0) for n in ADAM_SIZES]
     B = [tuple(t.clone() for t in tup) for tup in A]
     kw = dict(weight_decay=1e-2, decoupled=(mode == "adamw"))
     for step in range(1, 4):
@@ -127,10 +129,54 @@ def test_adam_dense_multi_equals_single_launches(device, mode):
             g.copy_(new_g); g2.copy_(new_g)
             if p.numel():
                 engine.adam_dense(p, g, m, v, step, 1e-3, zero_grad=True, **kw)
-        engine.adam_dense_multi(B, step, 1e-3, zero_grad=True, **kw)
+        for s0 in range(0, len(B), engine.ADAM_MULTI_MAX):
+            engine.adam_dense_flat([t + (None, 1) for t in B[s0:s0 + engine.ADAM_MULTI_MAX]], step, 1e-3, **kw)
     for ta, tb in zip(A, B):
         for x, y in zip(ta, tb):
             assert torch.equal(x, y)
+
+
+@pytest.mark.parametrize("zero_grad", [True, False])
+@pytest.mark.parametrize("mode", ["adam", "adamw"])
+def test_adam_step_groups_tensors_like_single_launches(device, mode, zero_grad):
+    """optim.Adam.step / AdamW.step — every tensor through yr_adam_dense_flat, grouped by step count and cut into
+    launches of ADAM_MULTI_MAX — equals one yr_adam_dense per tensor at that tensor's own step count, bit for bit:
+    more parameters than one launch takes, a table-sized one, one without a gradient, two one step ahead."""
+    from yelprecommendation_amd import engine, optim
+    rs = np.random.RandomState(4)
+    mk = lambda n: torch.from_numpy(rs.standard_normal(n).astype(np.float32)).to(device)
+    params = [torch.nn.Parameter(mk(n)) for n in ADAM_SIZES + [(1 << 18) + 4, 50]]
+    no_grad, ahead = len(params) - 1, (2, 9)
+    opt = (optim.AdamW if mode == "adamw" else optim.Adam)(params, lr=1e-3, weight_decay=1e-2)
+    for k in ahead:                                                            # as after one earlier step of their own
+        st = optim.adam_state(opt, params[k])
+        st["step"] = 1
+        st["exp_avg"].copy_(mk(params[k].numel()) * 0.1)
+        st["exp_avg_sq"].copy_(mk(params[k].numel()).abs() * 0.01)
+    want = []
+    for k, p in enumerate(params):
+        if k == no_grad:
+            want.append((p.detach().clone(),))
+            continue
+        p.grad = mk(p.numel())
+        st = opt.state.get(p, {})
+        m = st["exp_avg"].clone() if st else torch.zeros_like(p)
+        v = st["exp_avg_sq"].clone() if st else torch.zeros_like(p)
+        w, g = p.detach().clone(), p.grad.clone()
+        if p.numel():
+            engine.adam_dense(w, g, m, v, 2 if k in ahead else 1, 1e-3, weight_decay=1e-2,
+                              decoupled=(mode == "adamw"), zero_grad=zero_grad)
+        want.append((w, g, m, v))
+    opt.step(zero_grad=zero_grad)
+    for k, (p, w) in enumerate(zip(params, want)):
+        assert torch.equal(p.detach(), w[0]), k
+        if k == no_grad:
+            assert p.grad is None and not opt.state.get(p)
+            continue
+        st = opt.state[p]
+        assert st["step"] == (2 if k in ahead else 1)
+        assert torch.equal(p.grad, w[1]) and torch.equal(st["exp_avg"], w[2]) and torch.equal(st["exp_avg_sq"], w[3]), k
+        assert (float(p.grad.abs().sum()) == 0.0) == (zero_grad or p.numel() == 0)
 
 
 def test_sgd_dense(device):

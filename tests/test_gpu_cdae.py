@@ -414,10 +414,7 @@ def test_adam_flat_equals_adam_dense(device):
         want = [(p.clone(), m.clone(), v.clone()) for p, m, v in zip(P, M, V)]
         for (p, m, v), g in zip(want, Gd):
             flat = [t.reshape(-1) for t in (p, g.clone(), m, v)]
-            if flat[0].numel() % 4 == 0:
-                engine.adam_dense(*flat, 3, 1e-2, 0.9, 0.999, 1e-8, wd, decoupled=decoupled)
-            else:
-                engine.adam_dense_multi([tuple(flat)], 3, 1e-2, 0.9, 0.999, 1e-8, wd, decoupled=decoupled)
+            engine.adam_dense(*flat, 3, 1e-2, 0.9, 0.999, 1e-8, wd, decoupled=decoupled)
         tensors = [(p, g, m, v, marks if k == 2 else None, {0: 1, 1: 2}.get(k, 0))
                    for k, (p, g, m, v) in enumerate(zip(P, G, M, V))]
         engine.adam_dense_flat(tensors, 3, 1e-2, 0.9, 0.999, 1e-8, wd, decoupled=decoupled)

@@ -213,7 +213,7 @@ def test_whole_step_matches_reference_probe(g, device, tmp_path):
         want = g["grad:" + k]
         np.testing.assert_allclose(prm.grad.cpu().numpy(), want, rtol=1e-3, atol=1e-4 * max(1e-3, np.abs(want).max()),
                                    err_msg=k)
-    tr._optimizer_step()
+    tr.optimizer.step(zero_grad=True)
     lr = tr.cfg.lr
     for k, v in m.state_dict().items():
         tiny = np.abs(g["grad:" + k]) < 1e-6
@@ -244,7 +244,7 @@ def test_trainer_replay_matches_reference(g, device, tmp_path):
             sl = slice(start, start + int(s))
             u, p, n = (torch.from_numpy(g[f"train_{c}"][sl].astype(np.int64)).to(device) for c in "upn")
             got.append(float(tr.model.bpr_loss_backward(u, p, n).item()))
-            tr._optimizer_step()
+            tr.optimizer.step(zero_grad=True)
             start += int(s)
         ta += tsteps[e]
         vstart = int(vsz[:va].sum())

@@ -450,8 +450,13 @@ def test_batch_aware_propagation_equals_full_graph_propagation(device, tmp_path,
     assert float(a[4]["embedding.weight"].abs().sum()) > 0
 
 
-@pytest.mark.parametrize("batch,fraction,optimizer", [(24, 0.5, "adam"), (700, 0.5, "adamw"), (700, 0.0, "adam"), (24, 1e9, "adam")])
-def test_fused_step_equals_autograd_route(device, tmp_path, batch, fraction, optimizer):
+@pytest.mark.parametrize("batch,fraction,optimizer,layers,embed", [
+    (24, 0.5, "adam", 3, 64), (700, 0.5, "adamw", 3, 64), (700, 0.0, "adam", 3, 64), (24, 1e9, "adam", 3, 64),
+    # seven layers, the most yr_ngcf_bpr_step takes (K + 1 layer buffers <= YR_NGCF_MAX_LAYERS): 14 weight matrices
+    # in the step's one multi-tensor Adam launch
+    (24, 0.5, "adam", 7, 16)],
+    ids=["24-0.5-adam", "700-0.5-adamw", "700-0.0-adam", "24-1000000000.0-adam", "24-0.5-adam-7x16"])
+def test_fused_step_equals_autograd_route(device, tmp_path, batch, fraction, optimizer, layers, embed):
     """ngcf_step.NGCFStep (yr_ngcf_bpr_step: every launch of the step issued from C) against the autograd route
     (bpr_forward, zero_grad, BPRLoss, backward, optimizer.step) over six steps on changing batches: the same
     kernels on the same data — per-step losses bit-identical on the first step and equal to rounding after, all
@@ -472,7 +477,7 @@ def test_fused_step_equals_autograd_route(device, tmp_path, batch, fraction, opt
     out, first = {}, {}
     for route in ("fused", "autograd"):
         torch.manual_seed(8)
-        cfg = make_config("NGCF", embed_size=64, num_orders=3, device="cuda", model_dir=str(tmp_path),
+        cfg = make_config("NGCF", embed_size=embed, num_orders=layers, device="cuda", model_dir=str(tmp_path),
                           ngcf_subset_fraction=fraction)
         model = NGCF(cfg, nu, ni).to(device)
         with torch.no_grad():

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # YR_ENGINE_LIB: measurement hook — an instrumented build of the same sources (scratch/inst_build.sh writes it to
 # a temp directory so that the product objects and library are never overwritten); unset in every product run.
 LIB_PATH = os.environ.get("YR_ENGINE_LIB") or os.path.join(_HERE, "libyelprec_engine.so")
-ENGINE_VERSION = 29
+ENGINE_VERSION = 30
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -95,7 +95,6 @@ SIGNATURES = {
     "yr_bpr_loss_fwd": [_p, _p, _i64, _p, _p],
     "yr_bpr_loss_bwd": [_p, _p, _p, _f, _i64, _p, _p, _p],
     "yr_adam_dense": [_p, _p, _p, _p, _i64, _d, _d, _d, _d, _d, _d, _d, _int, _int, _p],
-    "yr_adam_dense_multi": [_p, _p, _p, _p, _p, _int, _d, _d, _d, _d, _d, _d, _d, _int, _int, _p],
     "yr_adam_dense_flat": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _int, _d, _d, _d, _d, _d, _d, _d, _int, _p],
     "yr_csr_rows_to_dense": [_p, _p, _p, _i64, _i64, _i64, _int, _p, _p, _p],
     "yr_negative_mask": [_p, _i64, _i64, _int, C.c_uint64, _p, _p, _p],

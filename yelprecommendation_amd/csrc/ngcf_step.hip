@@ -266,7 +266,7 @@ extern "C" int yr_ngcf_bpr_step(const int32_t* rowptr, const int32_t* col, const
     }
   }
 
-  // ---- optimizer.step(): dense Adam on the embedding table, one multi-tensor launch for the 2K weight matrices
+  // ---- optimizer.step(): dense Adam on the embedding table, one flat launch for the 2K weight matrices
   YR_TRY(yr_adam_dense(E0, dlayer(0), exp_avg[0], exp_avg_sq[0], n * D, lr, step_size, bc2_sqrt, beta1, beta2, eps,
                        weight_decay, mode, 0, stream));
   if (K > 0) {
@@ -276,8 +276,9 @@ extern "C" int yr_ngcf_bpr_step(const int32_t* rowptr, const int32_t* col, const
       g[t] = dW + (int64_t)t * dd;
       cnt[t] = dd;
     }
-    YR_TRY(yr_adam_dense_multi(params + 1, g, exp_avg + 1, exp_avg_sq + 1, cnt, 2 * K, lr, step_size, bc2_sqrt, beta1,
-                               beta2, eps, weight_decay, mode, 0, stream));
+    // no marks, no scaling, and the gradient is left alone (the next step's first launch clears dW)
+    YR_TRY(yr_adam_dense_flat(params + 1, g, exp_avg + 1, exp_avg_sq + 1, cnt, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, 2 * K, lr, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, mode, stream));
   }
   return launch_status();
 }

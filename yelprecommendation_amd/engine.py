@@ -1078,29 +1078,6 @@ def adam_dense(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_de
 ADAM_MULTI_MAX = 16
 
 
-def adam_dense_multi(tensors, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
-                     decoupled=False, zero_grad=False):
-    """The same Adam/AdamW step for several (p, g, m, v) tuples at the same step count in ONE launch
-    per ADAM_MULTI_MAX tensors — for the small weight matrices and biases of a model."""
-    import ctypes
-    lib = _lib.load()
-    step_size, bc2_sqrt = adam_scalars(step, lr, beta1, beta2)
-    f32 = torch.float32
-    for s0 in range(0, len(tensors), ADAM_MULTI_MAX):
-        group = tensors[s0:s0 + ADAM_MULTI_MAX]
-        cols = []
-        for k, name in enumerate("pgmv"):
-            cols.append((ctypes.c_void_p * len(group))(*[_dev(t[k], f32, name) for t in group]))
-        for p, g, m, v in group:
-            if not (p.numel() == g.numel() == m.numel() == v.numel()):
-                raise EngineError("p/g/m/v sizes differ")
-        counts = (ctypes.c_int64 * len(group))(*[t[0].numel() for t in group])
-        check(lib.yr_adam_dense_multi(cols[0], cols[1], cols[2], cols[3], counts, len(group), float(lr),
-                                      float(step_size), float(bc2_sqrt), float(beta1), float(beta2), float(eps),
-                                      float(weight_decay), OPT_ADAMW if decoupled else OPT_ADAM,
-                                      1 if zero_grad else 0, _stream()), "yr_adam_dense_multi")
-
-
 def adam_dense_flat(tensors, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, decoupled=False,
                     grad_count=None):
     """One launch, 16 bytes per lane, for up to ADAM_MULTI_MAX tensors of any size (yr_adam_dense_flat).

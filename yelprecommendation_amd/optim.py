@@ -36,7 +36,6 @@ class _DenseBase(Optimizer):
 
 class Adam(_DenseBase):
     _decoupled = False
-    SMALL = 1 << 18            # tensors up to this many elements share one multi-tensor launch
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -50,23 +49,20 @@ class Adam(_DenseBase):
             raise NotImplementedError("closure is not used by the reference trainers")
         for group in self.param_groups:
             b1, b2 = group["betas"]
-            small = {}                                   # step count -> [(p, g, m, v)] of the small tensors
+            by_step = {}                                 # step count -> [(p, g, m, v, no marks, clear)]
             for p in group["params"]:
                 g = self._grad(p)
                 if g is None:
                     continue
                 st = adam_state(self, p)
                 st["step"] += 1
-                if p.numel() <= self.SMALL:
-                    small.setdefault(st["step"], []).append((p.data, g, st["exp_avg"], st["exp_avg_sq"]))
-                    continue
-                engine.adam_dense(p.data, g, st["exp_avg"], st["exp_avg_sq"], st["step"], group["lr"],
-                                  b1, b2, group["eps"], group["weight_decay"],
-                                  decoupled=self._decoupled, zero_grad=zero_grad)
-            # weight matrices and biases: one launch for all of them instead of ~5 us each
-            for step, tensors in small.items():
-                engine.adam_dense_multi(tensors, step, group["lr"], b1, b2, group["eps"], group["weight_decay"],
-                                        decoupled=self._decoupled, zero_grad=zero_grad)
+                by_step.setdefault(st["step"], []).append(
+                    (p.data, g, st["exp_avg"], st["exp_avg_sq"], None, 1 if zero_grad else 0))
+            # tables, weight matrices and biases alike: one launch per ADAM_MULTI_MAX tensors instead of ~5 us each
+            for step, tensors in by_step.items():
+                for s0 in range(0, len(tensors), engine.ADAM_MULTI_MAX):
+                    engine.adam_dense_flat(tensors[s0:s0 + engine.ADAM_MULTI_MAX], step, group["lr"], b1, b2,
+                                           group["eps"], group["weight_decay"], decoupled=self._decoupled)
 
 
 class AdamW(Adam):

@@ -10,7 +10,8 @@ from abc import ABC, abstractmethod
 import torch
 from torch.nn import Module
 
-from .. import optim
+from .. import engine, optim
+from ..loss import BPRLoss
 from ..utils import logger
 
 
@@ -26,6 +27,8 @@ class BaseTrainer(ABC):
         self.cfg = cfg
         self.device: torch.device = self._device(cfg.device)
         os.makedirs(cfg.model_dir, exist_ok=True)
+        self._loss_accum = torch.zeros(1, dtype=torch.float64, device=self.device)
+        self._eval_hints = {}                              # eval set -> its last top-n lists (hints of the next evaluation)
 
     def _device(self, device_name: str) -> torch.device:
         """'cuda' is the ROCm device on MI355X.  'cpu' stays a legal name (the reference's default,
@@ -73,16 +76,52 @@ class BaseTrainer(ABC):
                 logger.info("[Trainer] update best model...")
                 best = tuple(current)
                 endurance = 0
-                torch.save(self.model.state_dict(), f'{self.cfg.model_dir}/best_model.pt')
+                self._save_best()
             else:
                 endurance += 1
                 if endurance > self.cfg.patience:
                     logger.info("[Trainer] ealry stopping...")
                     break
 
+    def _save_best(self):
+        torch.save(self.model.state_dict(), f'{self.cfg.model_dir}/best_model.pt')
+
     def _log_epoch(self, epoch, train_loss, valid_loss, p, r, m, n):
         logger.info(f"[Trainer] epoch: {epoch} > train loss: {train_loss:.4f} / valid loss: {valid_loss:.4f} / "
                     f"precision@K : {p:.4f} / Recall@K: {r:.4f} / MAP@K: {m:.4f} / NDCG@K: {n:.4f}")
+
+    def _log_test(self, p, r, m, n):
+        logger.info(f"[Trainer] Test > precision@{self.cfg.top_n} : {p:.4f} / Recall@{self.cfg.top_n}: {r:.4f} / "
+                    f"MAP@{self.cfg.top_n}: {m:.4f} / NDCG@{self.cfg.top_n}: {n:.4f}")
+
+    def _accumulate(self, loss):
+        # train_loss += loss.item() of the reference's loops without the per-step host sync
+        p = getattr(self, "_partials", None)
+        if p is None:
+            p = self._partials = torch.zeros(engine.LOSS_PARTIALS, dtype=torch.float32, device=self.device)
+        p[:1].copy_(loss.detach().reshape(1))
+        engine.loss_finalize(p, 1.0, None, self._loss_accum)
+
+    @staticmethod
+    def metrics_from_sums(sums):
+        """(precision, recall, map, ndcg) from [non-empty users, 4 sums, users] (engine.rank_metrics()[4:10])."""
+        cnt, ps, rs, ms, ns, total = sums.tolist()                 # the one read-back
+        return (ps / total, rs / cnt, ms / cnt, ns / cnt)
+
+    def _hinted_topk(self, key, U, I, users, mask_ptr, mask_idx, **kw):
+        """engine.mf_eval_topk under cfg.eval_precision ("bf16x3", the default: f32 scores from three-term bf16
+        splits, or "f32").  Evaluations under the same ``key`` hand their result to the next one as hint lists (the
+        lists start from the smallest score among a user's previous top-n under the CURRENT model — a bound the
+        result cannot depend on); ``key`` None or cfg.eval_hints=False turns that off."""
+        hinted = key is not None and self.cfg.get("eval_hints", True)
+        hint = self._eval_hints.get(key) if hinted else None
+        if hint is not None and tuple(hint.shape) != (users.numel(), self.cfg.top_n):
+            hint = None
+        top = engine.mf_eval_topk(U, I, users, mask_ptr, mask_idx, self.cfg.top_n,
+                                  precision=self.cfg.get("eval_precision", "bf16x3"), hint=hint, **kw)
+        if hinted:
+            self._eval_hints[key] = top
+        return top
 
     def _is_surpass_best_metric(self, **metric) -> bool:
         """``current`` beats ``best`` on ``cfg.best_metric`` (both are (valid_loss, precision, recall,
@@ -125,3 +164,37 @@ class BaseTrainer(ABC):
         logger.info("[Trainer] Load best model...")
         state = torch.load(f'{self.cfg.model_dir}/best_model.pt', map_location=self.device, weights_only=True)
         self.model.load_state_dict(state)
+
+
+class TripletTrainer(BaseTrainer):
+    """What the BPR-triplet trainers (MF, NGCF, DCN) share: the loss, the batch unpacking and the reference's
+    three-argument epoch loop, whose metrics come from ``evaluate(valid_eval_data, 'valid')``."""
+
+    def _loss(self):
+        return BPRLoss()
+
+    def run(self, train_dataloader, valid_dataloader, valid_eval_data):
+        # reference mf_trainer.py:34-97, ngcf_trainer.py:36-99, dcn_trainer.py:36-97
+        logger.info("[Trainer] run...")
+        best = (1e+6, .0, .0, .0, .0)
+        endurance = 0
+        for epoch in range(self.cfg.epochs):
+            train_loss = self.train(train_dataloader)
+            valid_loss = self.validate(valid_dataloader)
+            current = (valid_loss,) + tuple(self.evaluate(valid_eval_data, 'valid'))
+            self._log_epoch(epoch, train_loss, *current)
+            if self._is_surpass_best_metric(current=current, best=best):
+                logger.info("[Trainer] update best model...")
+                best = current
+                endurance = 0
+                self._save_best()
+            else:
+                endurance += 1
+                if endurance > self.cfg.patience:
+                    logger.info("[Trainer] ealry stopping...")
+                    break
+
+    def _batch(self, data):
+        dev = self.device
+        return (data['user_id'].to(dev, non_blocking=True), data['pos_item'].to(dev, non_blocking=True),
+                data['neg_item'].to(dev, non_blocking=True))

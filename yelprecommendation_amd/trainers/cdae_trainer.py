@@ -28,8 +28,6 @@ class CDAETrainer(BaseTrainer):
         self.model = CDAE(self.cfg, num_items, num_users)
         self.optimizer = self._optimizer(self.cfg.optimizer, self.model, self.cfg.lr)
         self.loss = self._loss()
-        self._loss_accum = torch.zeros(1, dtype=torch.float64, device=self.device)
-        self._partials = torch.zeros(engine.LOSS_PARTIALS, dtype=torch.float32, device=self.device)
         self._step = None                                  # the CDAEStep, kept across epochs
 
     def _loss(self):
@@ -41,10 +39,6 @@ class CDAETrainer(BaseTrainer):
         else:
             logger.error(f"Loss Not Exists: {self.cfg.loss_name} when negative_sampling == {self.cfg.negative_sampling}")
             raise NotImplementedError(f"Loss Not Exists: {self.cfg.loss_name}")
-
-    def _accumulate(self, loss):
-        self._partials[:1].copy_(loss.detach().reshape(1))
-        engine.loss_finalize(self._partials, 1.0, None, self._loss_accum)
 
     def _fused_step(self):
         """The CDAEStep bound to the model's parameters and the optimizer's Adam state (cdae_step.py), or None
@@ -169,15 +163,8 @@ class CDAETrainer(BaseTrainer):
         (sp, si), (ap, ai) = item_lists["seen"], item_lists["actual"]
         mask_value = engine.MASK_VALUE if model._output_act == engine.ACT_SIGMOID else 0.0
         # the previous lists of the same pass (validation / test) are the hint of this one (engine.mf_eval_topk)
-        hints = self.__dict__.setdefault("_eval_hints", {}) if self.cfg.get("eval_hints", True) else None
-        hint = hints.get(with_loss) if hints is not None else None
-        if hint is not None and tuple(hint.shape) != (model.num_users, self.cfg.top_n):
-            hint = None
-        top = engine.mf_eval_topk(Z, Wo, torch.arange(model.num_users, device=dev), sp, si, self.cfg.top_n,
-                                  mask_value=mask_value, item_bias=bo,
-                                  precision=self.cfg.get("eval_precision", "bf16x3"), hint=hint)
-        if hints is not None:
-            hints[with_loss] = top
+        top = self._hinted_topk(with_loss, Z, Wo, torch.arange(model.num_users, device=dev), sp, si,
+                                mask_value=mask_value, item_bias=bo)
         model.check_indices()
         return engine.rank_metrics(top, ap, ai)[4:10]
 
@@ -188,8 +175,7 @@ class CDAETrainer(BaseTrainer):
         if getattr(valid_dataloader, "lists", False):
             with torch.no_grad():
                 sums = self._scored_by_lists(valid_dataloader, with_loss=True)
-            p, r, m, n = self._metrics(False, None, None, sums)
-            return (float(self._loss_accum.item()), p, r, m, n)
+            return (float(self._loss_accum.item()),) + self.metrics_from_sums(sums)
         actual, predicted = [], []
         host = self.cfg.get("host_metrics", False)
         sums = torch.zeros(6, dtype=torch.float64, device=self.device)
@@ -221,9 +207,8 @@ class CDAETrainer(BaseTrainer):
         if getattr(test_dataloader, "lists", False):
             with torch.no_grad():
                 sums = self._scored_by_lists(test_dataloader, with_loss=False)
-            p, r, m, n = self._metrics(False, None, None, sums)
-            logger.info(f"[Trainer] Test > precision@{self.cfg.top_n} : {p:.4f} / Recall@{self.cfg.top_n}: {r:.4f} / "
-                        f"MAP@{self.cfg.top_n}: {m:.4f} / NDCG@{self.cfg.top_n}: {n:.4f}")
+            p, r, m, n = self.metrics_from_sums(sums)
+            self._log_test(p, r, m, n)
             return (p, r, m, n)
         actual, predicted = [], []
         host = self.cfg.get("host_metrics", False)
@@ -240,15 +225,13 @@ class CDAETrainer(BaseTrainer):
                 else:
                     sums += self._metric_sums(pred, test_mask, input_mask, data.get('item_lists'))
         p, r, m, n = self._metrics(host, actual, predicted, sums)
-        logger.info(f"[Trainer] Test > precision@{self.cfg.top_n} : {p:.4f} / Recall@{self.cfg.top_n}: {r:.4f} / "
-                    f"MAP@{self.cfg.top_n}: {m:.4f} / NDCG@{self.cfg.top_n}: {n:.4f}")
+        self._log_test(p, r, m, n)
         return (p, r, m, n)
 
     def _metrics(self, host, actual, predicted, sums):
         if host:
             return ranking_metrics(actual, np.concatenate(predicted, axis=0).tolist(), self.cfg.top_n)
-        cnt, ps, rs, ms, ns, total = sums.tolist()                 # the one read-back
-        return (ps / total, rs / cnt, ms / cnt, ns / cnt)
+        return self.metrics_from_sums(sums)
 
     @staticmethod
     def _rows_to_csr(mask):
@@ -278,9 +261,6 @@ class CDAETrainer(BaseTrainer):
         # reference cdae_trainer.py:123-144
         actual = [np.nonzero(row)[0] for row in actual_mask.cpu().numpy()]
         # CSR of the seen items per row (index bookkeeping only), masked scores become 0 in the kernel
-        nz = pred_mask.nonzero()
-        counts = torch.bincount(nz[:, 0], minlength=pred_mask.shape[0])
-        ptr = torch.zeros(pred_mask.shape[0] + 1, dtype=torch.int64, device=pred.device)
-        ptr[1:] = torch.cumsum(counts, 0)
-        top = engine.topk_masked(pred.detach().contiguous(), ptr, nz[:, 1].contiguous(), self.cfg.top_n, mask_value=0.0)
+        ptr, idx = self._rows_to_csr(pred_mask)
+        top = engine.topk_masked(pred.detach().contiguous(), ptr, idx, self.cfg.top_n, mask_value=0.0)
         return actual, [top.cpu().numpy()]

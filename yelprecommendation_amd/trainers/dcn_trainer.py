@@ -9,24 +9,20 @@ Differences underneath (results equal to float rounding):
 * the attributes come from the device table ``cat_ids`` / ``sc_ids`` (DCNDataPipeline) instead of four per-item dict
   lookups per batch (dcn_trainer.py:106-109);
 * a training step is DCN.bpr_loss_backward (gather, deep-tower GEMMs, one fused head kernel, scatter) and one Adam
-  launch over all tensors (yr_adam_dense_flat); the running loss stays on the device;
+  launch over all tensors (optimizer.step: yr_adam_dense_flat); the running loss stays on the device;
 * ``evaluate`` scores all eval users against the whole catalogue with the fused scorer (yr_dcn_score) instead of one
   user at a time in chunks of ``batch_size`` items (dcn_trainer.py:145-165), then masks (``pred[mask] = 0``) and
   takes the top-n on the device.  Ties (the sigmoid saturates at 1.0f) are ordered by item id.
 """
-import numpy as np
 import torch
 
 from .. import engine
-from .. import optim
-from ..loss import BPRLoss
 from ..models.dcn import DCN
-from ..utils import logger
-from .base_trainer import BaseTrainer
-from .mf_trainer import eval_csr
+from .base_trainer import TripletTrainer
+from .eval_set import EvalSets
 
 
-class DCNTrainer(BaseTrainer):
+class DCNTrainer(TripletTrainer):
     EVAL_CHUNK = 4096                 # users per score buffer (4096 x 38,048 f32 = 623 MB)
 
     def __init__(self, cfg, num_items: int, num_users: int, item2attributes=None, attributes_count=None,
@@ -42,55 +38,7 @@ class DCNTrainer(BaseTrainer):
         if cat_ids is None:
             cat_ids, sc_ids = _tables_from_dict(item2attributes, num_items)
         self.model.set_item_attributes(cat_ids, sc_ids)
-        self._loss_accum = torch.zeros(1, dtype=torch.float64, device=self.device)
-        self._eval_cache = {}
-
-    def _loss(self):
-        return BPRLoss()
-
-    def run(self, train_dataloader, valid_dataloader, valid_eval_data):
-        # reference dcn_trainer.py:36-97
-        logger.info("[Trainer] run...")
-        best = (1e+6, .0, .0, .0, .0)
-        endurance = 0
-        for epoch in range(self.cfg.epochs):
-            train_loss = self.train(train_dataloader)
-            valid_loss = self.validate(valid_dataloader)
-            current = (valid_loss,) + tuple(self.evaluate(valid_eval_data, 'valid'))
-            self._log_epoch(epoch, train_loss, *current)
-            if self._is_surpass_best_metric(current=current, best=best):
-                logger.info("[Trainer] update best model...")
-                best = current
-                endurance = 0
-                torch.save(self.model.state_dict(), f'{self.cfg.model_dir}/best_model.pt')
-            else:
-                endurance += 1
-                if endurance > self.cfg.patience:
-                    logger.info("[Trainer] ealry stopping...")
-                    break
-
-    def _batch(self, data):
-        dev = self.device
-        return (data['user_id'].to(dev, non_blocking=True), data['pos_item'].to(dev, non_blocking=True),
-                data['neg_item'].to(dev, non_blocking=True))
-
-    def _optimizer_step(self):
-        """optimizer.step() + zero_grad(): Adam / AdamW as yr_adam_dense_flat launches over all DCN tensors (10 + 2L,
-        up to ADAM_MULTI_MAX per launch); other optimizers through their own step()."""
-        if not isinstance(self.optimizer, optim.Adam):
-            self.optimizer.step(zero_grad=True)
-            return
-        group = self.optimizer.param_groups[0]
-        b1, b2 = group["betas"]
-        tensors, step = [], None
-        for p in group["params"]:
-            st = optim.adam_state(self.optimizer, p)
-            st["step"] += 1
-            step = st["step"]
-            tensors.append((p.data, p.grad, st["exp_avg"], st["exp_avg_sq"], None, 1))
-        for s0 in range(0, len(tensors), engine.ADAM_MULTI_MAX):
-            engine.adam_dense_flat(tensors[s0:s0 + engine.ADAM_MULTI_MAX], step, group["lr"], b1, b2, group["eps"],
-                                   group["weight_decay"], decoupled=self.optimizer._decoupled)
+        self._eval_sets = EvalSets(self.device)
 
     def train(self, train_dataloader) -> float:
         # reference dcn_trainer.py:100-118
@@ -99,7 +47,7 @@ class DCNTrainer(BaseTrainer):
         for data in train_dataloader:
             user_id, pos_item, neg_item = self._batch(data)
             self.model.bpr_loss_backward(user_id, pos_item, neg_item, loss_accum=self._loss_accum)
-            self._optimizer_step()
+            self.optimizer.step(zero_grad=True)
         self.model.check_indices()
         return float(self._loss_accum.item())
 
@@ -115,14 +63,7 @@ class DCNTrainer(BaseTrainer):
 
     # -- evaluation ---------------------------------------------------------------------------------
     def _eval_arrays(self, eval_data, limit=None):
-        key = (id(eval_data), limit)
-        if key not in self._eval_cache:
-            part = eval_data if limit is None else eval_data[:limit]
-            users = np.asarray(part.index.values, dtype=np.int64)
-            pos = [list(x) for x in part['pos_items']]
-            masks = [list(x) for x in part['mask_items']]
-            self._eval_cache[key] = (eval_data,) + eval_csr(users, pos, masks, self.device)
-        return self._eval_cache[key]
+        return self._eval_sets.eval_set(eval_data, limit=limit)
 
     @torch.no_grad()
     def recommend(self, users, mask_ptr, mask_idx):
@@ -150,8 +91,7 @@ class DCNTrainer(BaseTrainer):
         predicted = self.recommend(users, mask_ptr, mask_idx)
         p, r, m, n = engine.rank_metrics(predicted, pos_ptr, pos_idx)[:4].tolist()
         if mode == 'test':
-            logger.info(f"[Trainer] Test > precision@{self.cfg.top_n} : {p:.4f} / Recall@{self.cfg.top_n}: {r:.4f} / "
-                        f"MAP@{self.cfg.top_n}: {m:.4f} / NDCG@{self.cfg.top_n}: {n:.4f}")
+            self._log_test(p, r, m, n)
         return (p, r, m, n)
 
 

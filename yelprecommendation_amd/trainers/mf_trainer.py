@@ -23,17 +23,15 @@ it owns (the epoch is cut by owner once, on the device), the item gradient is al
 user rows are exchanged once per epoch, ``evaluate`` scores only the rank's users and sums the
 per-user metric terms with one 6-double all-reduce, and only rank 0 writes ``best_model.pt``.
 """
-import numpy as np
 import torch
 
 from .. import engine
 from ..bpr_step import BPRMFStep
-from ..loss import BPRLoss
 from ..metric import ranking_metrics
 from ..models.mf import MatrixFactorization
 from ..user_shard import UserShard
-from ..utils import logger
-from .base_trainer import BaseTrainer
+from .base_trainer import TripletTrainer
+from .eval_set import EvalSets, top_k_of_scores
 
 
 def _dist():
@@ -44,24 +42,7 @@ def _dist():
     return None
 
 
-def _lists_to_csr(lists):
-    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
-    np.cumsum([len(l) for l in lists], out=ptr[1:])
-    idx = np.fromiter((x for l in lists for x in l), dtype=np.int64, count=int(ptr[-1]))
-    return ptr, idx
-
-
-def eval_csr(users, pos, masks, device):
-    """(pos lists, users, mask_ptr, mask_idx, pos_ptr, pos_idx) of an evaluation set on the device: the held-out
-    lists in their original order (the metrics depend on it) and the mask lists as CSR."""
-    mask_ptr, mask_idx = _lists_to_csr(masks)
-    pos_ptr, pos_idx = _lists_to_csr(pos)
-    return (pos, torch.from_numpy(users).to(device), torch.from_numpy(mask_ptr).to(device),
-            torch.from_numpy(mask_idx).to(device), torch.from_numpy(pos_ptr).to(device),
-            torch.from_numpy(pos_idx).to(device))
-
-
-class MFTrainer(BaseTrainer):
+class MFTrainer(TripletTrainer):
     def __init__(self, cfg, num_items: int, num_users: int) -> None:
         super().__init__(cfg)
         self.num_items = num_items
@@ -69,46 +50,18 @@ class MFTrainer(BaseTrainer):
         self.model = MatrixFactorization(self.cfg, num_users, num_items).to(self.device)
         self.optimizer = self._optimizer(self.cfg.optimizer, self.model, self.cfg.lr, self.cfg.weight_decay)
         self.loss = self._loss()
-        self._loss_accum = torch.zeros(1, dtype=torch.float64, device=self.device)
-        self._eval_cache = {}
-        self._eval_hints = {}                              # eval set -> its last top-n lists (hints of the next evaluation)
+        self._eval_sets = EvalSets(self.device)
         dist = _dist()
         self.world_size = dist.get_world_size() if dist else 1
         self.rank = dist.get_rank() if dist else 0
         self.shard = UserShard(num_users, self.world_size, self.rank)
         self._step = None                                  # the BPRMFStep, kept across epochs
 
-    def _loss(self):
-        return BPRLoss()
-
-    def run(self, train_dataloader, valid_dataloader, valid_eval_data):
-        # reference mf_trainer.py:34-97
-        logger.info("[Trainer] run...")
-        best = (1e+6, .0, .0, .0, .0)
-        endurance = 0
-        for epoch in range(self.cfg.epochs):
-            train_loss = self.train(train_dataloader)
-            valid_loss = self.validate(valid_dataloader)
-            current = (valid_loss,) + tuple(self.evaluate(valid_eval_data, 'valid'))
-            self._log_epoch(epoch, train_loss, *current)
-            if self._is_surpass_best_metric(current=current, best=best):
-                logger.info("[Trainer] update best model...")
-                best = current
-                endurance = 0
-                if self.rank == 0:
-                    torch.save(self.model.state_dict(), f'{self.cfg.model_dir}/best_model.pt')
-                if self.world_size > 1:
-                    _dist().barrier()                      # the file is complete before anyone loads it
-            else:
-                endurance += 1
-                if endurance > self.cfg.patience:
-                    logger.info("[Trainer] ealry stopping...")
-                    break
-
-    def _batch(self, data):
-        dev = self.device
-        return (data['user_id'].to(dev, non_blocking=True), data['pos_item'].to(dev, non_blocking=True),
-                data['neg_item'].to(dev, non_blocking=True))
+    def _save_best(self):
+        if self.rank == 0:
+            super()._save_best()
+        if self.world_size > 1:
+            _dist().barrier()                              # the file is complete before anyone loads it
 
     def _fused_step(self):
         """A BPRMFStep over the model's tables and the optimizer's own Adam state (created on
@@ -290,39 +243,23 @@ class MFTrainer(BaseTrainer):
         return float(self._loss_accum.item())
 
     # -- evaluation -------------------------------------------------------------------------
+    def _eval_set(self, eval_data):
+        # masks sorted for the fused evaluation kernel; under user sharding this rank scores the users it owns
+        return self._eval_sets.eval_set(eval_data, sort_masks=True,
+                                        keep=self.shard.mine if self.world_size > 1 else None)
+
     def _eval_arrays(self, eval_data):
         """eval_data: DataFrame indexed by user_id with list columns 'pos_items' and
         'mask_items' (reference mf_data_pipeline.py:49-50).  Cached CSR + device copies."""
-        key = id(eval_data)
-        if key not in self._eval_cache:
-            users = np.asarray(eval_data.index.values, dtype=np.int64)
-            pos = [list(x) for x in eval_data['pos_items']]
-            # ascending ids inside every mask list: what the fused evaluation kernel walks with a cursor
-            # (sorted once here instead of on the device at every evaluate())
-            masks = [sorted(x) for x in eval_data['mask_items']]
-            if self.world_size > 1:                            # this rank scores the users it owns
-                keep = np.flatnonzero(self.shard.mine(users))
-                users, pos, masks = users[keep], [pos[k] for k in keep], [masks[k] for k in keep]
-            self._eval_cache[key] = (eval_data,) + eval_csr(users, pos, masks, self.device)
-        return self._eval_cache[key][1:5]
+        return self._eval_set(eval_data)[1:5]
 
     def recommend(self, users, mask_ptr, mask_idx, hint_key=None):
         """Top-``top_n`` item ids per user, masked items excluded ([n_users, top_n] int64, device).
         ``hint_key``: evaluations under the same key hand their result to the next one as hint lists
-        (engine.mf_eval_topk: the lists start from the smallest score among a user's previous top-n under the
-        CURRENT model — a bound the result cannot depend on; cfg.eval_hints=False turns it off)."""
+        (BaseTrainer._hinted_topk; cfg.eval_hints=False turns it off)."""
         U, I = self.model.user_embedding.weight.detach(), self.model.item_embedding.weight.detach()
         if engine.fused_eval_supports(self.cfg.top_n, U.shape[1]):   # fused scores + mask + top-k; masks are pre-sorted
-            # cfg.eval_precision: "bf16x3" (default; f32 scores from three-term bf16 splits) or "f32"
-            hinted = hint_key is not None and self.cfg.get("eval_hints", True)
-            hint = self._eval_hints.get(hint_key) if hinted else None
-            if hint is not None and tuple(hint.shape) != (users.numel(), self.cfg.top_n):
-                hint = None
-            top = engine.mf_eval_topk(U, I, users.contiguous(), mask_ptr, mask_idx, self.cfg.top_n,
-                                      precision=self.cfg.get("eval_precision", "bf16x3"), hint=hint)
-            if hinted:
-                self._eval_hints[hint_key] = top
-            return top
+            return self._hinted_topk(hint_key, U, I, users.contiguous(), mask_ptr, mask_idx)
         return engine.mf_recommend(U, I, users, mask_ptr, mask_idx, self.cfg.top_n, fused=False)
 
     def evaluate(self, eval_data, mode='valid') -> tuple:
@@ -337,29 +274,22 @@ class MFTrainer(BaseTrainer):
             p, r, m, n = ranking_metrics(actual, predicted.cpu().numpy().tolist(), self.cfg.top_n)
         else:
             predicted = self.recommend(users, mask_ptr, mask_idx, hint_key=id(eval_data))
-            pos_ptr, pos_idx = self._eval_cache[id(eval_data)][5:7]
+            pos_ptr, pos_idx = self._eval_set(eval_data)[5:7]
             p, r, m, n = engine.rank_metrics(predicted, pos_ptr, pos_idx)[:4].tolist()
         if mode == 'test':
-            logger.info(f"[Trainer] Test > precision@{self.cfg.top_n} : {p:.4f} / Recall@{self.cfg.top_n}: {r:.4f} / "
-                        f"MAP@{self.cfg.top_n}: {m:.4f} / NDCG@{self.cfg.top_n}: {n:.4f}")
+            self._log_test(p, r, m, n)
         return (p, r, m, n)
 
     def _evaluate_sharded(self, eval_data, users, mask_ptr, mask_idx):
         """Metrics over ALL eval users from per-rank sums: [non-empty users, 4 sums, users]."""
         sums = torch.zeros(6, dtype=torch.float64, device=self.device)
         if users.numel():
-            pos_ptr, pos_idx = self._eval_cache[id(eval_data)][5:7]
+            pos_ptr, pos_idx = self._eval_set(eval_data)[5:7]
             sums = engine.rank_metrics(self.recommend(users, mask_ptr, mask_idx, hint_key=id(eval_data)), pos_ptr,
                                        pos_idx)[4:10].clone()
         _dist().all_reduce(sums)
-        cnt, ps, rs, ms, ns, total = sums.tolist()
-        return (ps / total, rs / cnt, ms / cnt, ns / cnt)
+        return self.metrics_from_sums(sums)
 
     def _generate_top_k_recommendation(self, pred, mask_items):
-        """reference mf_trainer.py:163-178 for ONE user's score vector (kept for callers
-        that score users one at a time); the batched path is :meth:`recommend`."""
-        dev = pred.device
-        mask = torch.as_tensor(np.asarray(mask_items, dtype=np.int64), device=dev)
-        ptr = torch.tensor([0, mask.numel()], dtype=torch.int64, device=dev)
-        top = engine.topk_masked(pred.detach().reshape(1, -1).contiguous(), ptr, mask, self.cfg.top_n)
-        return top[0].cpu().numpy()
+        # one user's score vector; the batched path is :meth:`recommend`
+        return top_k_of_scores(pred, mask_items, self.cfg.top_n)

@@ -12,15 +12,14 @@ import numpy as np
 import torch
 
 from .. import engine
-from ..loss import BPRLoss
 from ..metric import ranking_metrics
 from ..models.ngcf import NGCF, _iadd
 from ..utils import logger
-from .base_trainer import BaseTrainer
-from .mf_trainer import _lists_to_csr
+from .base_trainer import TripletTrainer
+from .eval_set import _lists_to_csr, top_k_of_scores
 
 
-class NGCFTrainer(BaseTrainer):
+class NGCFTrainer(TripletTrainer):
     def __init__(self, cfg, num_items: int, num_users: int, laplacian_matrix) -> None:
         super().__init__(cfg)
         logger.info(f'[DEVICE] device = {self.device}')
@@ -30,47 +29,6 @@ class NGCFTrainer(BaseTrainer):
         self.optimizer = self._optimizer(self.cfg.optimizer, self.model, self.cfg.lr, self.cfg.weight_decay)
         self.loss = self._loss()
         self.laplacian_matrix = laplacian_matrix
-        self._loss_accum = torch.zeros(1, dtype=torch.float64, device=self.device)
-
-    def _loss(self):
-        return BPRLoss()
-
-    def run(self, train_dataloader, valid_dataloader, valid_eval_data):
-        # reference ngcf_trainer.py:36-99
-        logger.info("[Trainer] run...")
-        best = (1e+6, .0, .0, .0, .0)
-        endurance = 0
-        for epoch in range(self.cfg.epochs):
-            train_loss = self.train(train_dataloader)
-            valid_loss = self.validate(valid_dataloader)
-            current = (valid_loss,) + tuple(self.evaluate(valid_eval_data, 'valid'))
-            self._log_epoch(epoch, train_loss, *current)
-            if self._is_surpass_best_metric(current=current, best=best):
-                logger.info("[Trainer] update best model...")
-                best = current
-                endurance = 0
-                torch.save(self.model.state_dict(), f'{self.cfg.model_dir}/best_model.pt')
-            else:
-                endurance += 1
-                if endurance > self.cfg.patience:
-                    logger.info("[Trainer] ealry stopping...")
-                    break
-
-    def _batch(self, data):
-        dev = self.device
-        return (data['user_id'].to(dev, non_blocking=True), data['pos_item'].to(dev, non_blocking=True),
-                data['neg_item'].to(dev, non_blocking=True))
-
-    def _accumulate(self, loss):
-        # train_loss += loss.item() of ngcf_trainer.py:116 without the per-step host sync
-        engine.loss_finalize(self._one_partial(loss), 1.0, None, self._loss_accum)
-
-    def _one_partial(self, loss):
-        p = getattr(self, "_partials", None)
-        if p is None:
-            p = self._partials = torch.zeros(engine.LOSS_PARTIALS, dtype=torch.float32, device=self.device)
-        p[:1].copy_(loss.detach().reshape(1))
-        return p
 
     def _fused_step(self):
         """The whole batch step as one engine call (ngcf_step.NGCFStep) for Adam / AdamW unless
@@ -153,13 +111,8 @@ class NGCFTrainer(BaseTrainer):
                                    torch.from_numpy(mask_idx).to(dev)).cpu().numpy()
         p, r, m, n = ranking_metrics(actual, predicted.tolist(), self.cfg.top_n)
         if mode == 'test':
-            logger.info(f"[Trainer] Test > precision@{self.cfg.top_n} : {p:.4f} / Recall@{self.cfg.top_n}: {r:.4f} / "
-                        f"MAP@{self.cfg.top_n}: {m:.4f} / NDCG@{self.cfg.top_n}: {n:.4f}")
+            self._log_test(p, r, m, n)
         return (p, r, m, n)
 
     def _generate_top_k_recommendation(self, pred, mask_items):
-        # reference ngcf_trainer.py:167-182 for one user's score vector
-        dev = pred.device
-        mask = torch.as_tensor(np.asarray(mask_items, dtype=np.int64), device=dev)
-        ptr = torch.tensor([0, mask.numel()], dtype=torch.int64, device=dev)
-        return engine.topk_masked(pred.detach().reshape(1, -1).contiguous(), ptr, mask, self.cfg.top_n)[0].cpu().numpy()
+        return top_k_of_scores(pred, mask_items, self.cfg.top_n)
