@@ -17,7 +17,9 @@
  *     asynchronous on it; functions are stateless and re-entrant;
  *   - tables are row-major contiguous float32 [rows, D]; indices are int64 (what the
  *     reference's DataLoader yields: data/datasets/mf_dataset.py:26-31);
- *   - supported embedding widths D: 16, 32, 64, 128 (YR_ERR_UNSUPPORTED otherwise);
+ *   - supported embedding widths D: 16, 32, 64, 128 (YR_ERR_UNSUPPORTED otherwise); the BPR-MF push-form calls
+ *     (yr_mf_score, yr_mf_score_backward, yr_bpr_mf_fwd_bwd, yr_bpr_mf_scatter_step), yr_mf_scores_gemm and
+ *     yr_mf_eval_topk[_bias] also take the wide widths 256, 512 and 1024;
  *   - return value: 0 on success, a positive hipError_t if a launch failed, or a
  *     negative YR_ERR_* for a rejected argument.  Nothing throws.
  *   - `err_flag` (int32, device, may be NULL): kernels that consume indices OR a
@@ -114,7 +116,9 @@ int yr_bpr_mf_fwd_bwd(const float *U, const float *I,
  * yr_adam_dense_dual on its own: p0/p1 any two tensors with n0/n1 elements (multiples of 4),
  * touched0/touched1 per row of `row_width` elements or NULL (gradient always read and cleared);
  * with marks, row_width / 4 must divide 64 (the lanes of a row share one wave: 4, 8, 16, 32, 64, 128,
- * 256 — anything else is YR_ERR_BADARG); loss_partials NULL = no loss reduction.
+ * 256 — anything else is YR_ERR_BADARG; yr_bpr_mf_scatter_step itself also takes D = 512 and 1024: there the
+ * lanes of a row share one workgroup iteration and meet at a barrier before the mark is cleared);
+ * loss_partials NULL = no loss reduction.
  * ------------------------------------------------------------------------- */
 int yr_bpr_mf_scatter_step(float *U, float *I, float *gradU, float *gradI,
                            float *mU, float *vU, float *mI, float *vI, uint8_t *touched,
@@ -146,7 +150,8 @@ int yr_adam_dense_dual(float *p0, float *g0, float *m0, float *v0, int64_t n0,
  * LDS and walks the sorted stream: scores, loss, user gradient in registers, Adam -> U_new; one
  * coefficient per triplet for the item side) and an owner pass over the item buckets (item gradient from the OLD user
  * rows, Adam in place; its first workgroup also reduces the loss partials in fixed order).
- * Limits: rows / (1024/D) <= 16383 buckets per table, num_users < 2^26 (YR_ERR_UNSUPPORTED beyond).
+ * Limits: D <= 128 (the wide widths 256 .. 1024 train with the push form only: a bucket would hold 4 .. 1 rows);
+ * rows / (1024/D) <= 16383 buckets per table, num_users < 2^26 (YR_ERR_UNSUPPORTED beyond).
  *
  *   U_old  [num_users, D]  read;  U_new [num_users, D] written (must not alias U_old:
  *          the caller ping-pongs the two buffers between steps);
@@ -501,6 +506,8 @@ int yr_mf_scores_gemm(const float *U, const float *I, const int64_t *users, int6
  *   scores of the items in mask_idx[mask_ptr[r] .. mask_ptr[r+1]) to mask_value; score
  *   descending, item id ascending among equal scores.  k <= 32 (the lists live in registers: 4, 10, 16 or 32
  *   entries); k > 16 up to D = 64 only (YR_ERR_UNSUPPORTED beyond: yr_mf_scores_gemm + yr_topk_masked).
+ *   D = 256, 512, 1024 (k <= 16): a sweep that walks D in slabs with the accumulators live across them — the same
+ *   lists; it runs no prescan and has one form (the prescan and form flags below are accepted and change nothing).
  * The mask lists must be sorted ASCENDING inside each row (the kernel walks them with a cursor as
  * it sweeps the catalogue).  mask_ptr may be NULL.
  * mode: how the matrix cores compute the f32 scores —

@@ -38,6 +38,15 @@ BUDGETS = [
     (r"void yr::ngcf_dense_bwd_data_kernel<64, false>", 128, 0, "as the forward kernel"),
     (r"void yr::ngcf_dense_(fwd|bwd_data)_kernel<64, true>", 168, 0,
      "row-list forms: three waves per SIMD (a hoisted weight tile once took the forward kernel to 252)"),
+    # the wide widths (256 / 512 / 1024) of BPR-MF
+    (r"void yr::bpr_fwd_bwd_kernel<(256|512|1024), (true|false), (16|64|256)>", 96, 4 * 1024,
+     "push form, wide rows: 24 row registers in flight (RowGeom::UNROLL), five waves per SIMD (512 / 5 -> 96)"),
+    (r"void yr::mf_score(_backward)?_kernel<(256|512|1024)>", 64, 4 * 1024, "as the narrow widths: eight waves per SIMD"),
+    (r"void yr::mf_eval_topk_wide_kernel<(256|512|1024), (4|10|16), (true|false), (true|false)>", 256, 72 * 1024,
+     "slab sweep: two workgroups of four waves per CU = two waves per SIMD (512 / 2 -> 256), 2 x 72 KB of 160 KB LDS"),
+    (r"void yr::mf_scores_mfma_wide_kernel<(256|512|1024)>", 256, 72 * 1024, "score GEMM in slabs: as the sweep"),
+    (r"void yr::et_hint_bound_kernel<(256|512|1024)>", 64, 0, "the dot product is a loop: eight waves per SIMD"),
+    (r"void yr::adam_dual_wide_kernel<(true|false)>", 64, 1024, "streaming pass, as adam_dual_kernel"),
 ]
 # Scratch (spilled registers) per lane.  The forms the benchmark and the trainers run by default — width 64, summation
 # order free — must have none; the deterministic-order forms and some forms of the other widths are held at 64 VGPRs by

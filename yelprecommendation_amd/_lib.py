@@ -171,7 +171,7 @@ def check(status: int, what: str):
     if status == 0:
         return
     if status == -1:
-        raise EngineError(f"{what}: unsupported configuration (embedding width must be 16/32/64/128)")
+        raise EngineError(f"{what}: unsupported configuration (embedding width must be 16/32/64/128, or 256/512/1024 on the BPR-MF push, evaluation and score paths; top-k above 16 needs a width up to 64)")
     if status == -2:
         raise EngineError(f"{what}: bad argument (null pointer, negative size or misaligned buffer)")
     raise EngineError(f"{what}: HIP error {status}")

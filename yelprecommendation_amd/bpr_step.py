@@ -51,6 +51,17 @@ class BPRMFStep:
         gradient, then a separate dense Adam launch) even with one rank — used by tests."""
         if item_exchange not in ("all_reduce", "reduce_scatter"):
             raise ValueError("item_exchange must be 'all_reduce' or 'reduce_scatter'")
+        # the wide widths run the push (atomic) form only: every option that needs the pull form is refused here,
+        # not by a late error out of the pull workspace call
+        width = int(U.shape[1])
+        if width in engine.WIDE_WIDTHS:
+            limit = max(engine.SUPPORTED_WIDTHS)
+            for wanted, what in ((impl == "pull", 'impl="pull"'), (bool(deterministic), "deterministic=True"),
+                                 (item_exchange == "reduce_scatter", 'item_exchange="reduce_scatter"')):
+                if wanted:
+                    raise NotImplementedError(
+                        f"BPRMFStep: {what} needs the pull form, which covers embedding widths up to {limit}; "
+                        f"width {width} trains with the push form only (impl=\"auto\" or \"atomic\")")
         # N > 1 only.  "all_reduce": the item gradient is summed everywhere and every rank applies the same
         # dense Adam to its replica (item Adam state replicated).  "reduce_scatter": rank r receives the
         # summed gradient of ITS slice of the item rows, applies Adam to that slice alone (1/N of the

@@ -42,4 +42,12 @@ __device__ __forceinline__ void adam_element(float& p, float grad, float& m, flo
   p = p + (c.neg_step * m) / denom;               // addcdiv_
 }
 
+// yr_adam_dense_dual (csrc/optim.hip) for callers inside the library; wide_marks: rows of 512 and 1,024 floats may
+// carry touched marks (yr_bpr_mf_scatter_step, csrc/bpr_mf.hip)
+int adam_dense_dual_launch(float* p0, float* g0, float* m0, float* v0, int64_t n0, float* p1, float* g1, float* m1,
+                           float* v1, int64_t n1, int row_width, uint8_t* touched0, uint8_t* touched1, double lr,
+                           double step_size, double bc2_sqrt, double beta1, double beta2, double eps,
+                           double weight_decay, int mode, const float* loss_partials, float loss_scale,
+                           float* loss_out, double* loss_accum, void* stream, bool wide_marks);
+
 }  // namespace yr

@@ -7,16 +7,17 @@
 //
 // Layout: tables are row-major float32 [rows, D].  One row lives on LPR = min(D,64)
 // lanes (element l + 64*j on lane l), so every load, store and float atomic of a row
-// is one or two wave-instructions over 256 (128 for D=32, 64 for D=16) contiguous
+// is D / 64 (one below D = 128) wave-instructions over 256 (128 for D=32, 64 for D=16) contiguous
 // bytes — the access shape the memory-side float atomics sustain their full rate on.
 // The (u, i, j) triplets of a tile are staged through LDS once (coalesced 8-byte
 // loads, range-checked, narrowed to int32) and then broadcast-read by the waves.
+#include "adam.h"
 #include "common.h"
 
 namespace yr {
 
 constexpr int kTile = kBlock;   // triplets staged per workgroup iteration
-constexpr int kUnroll = 4;      // row groups in flight per wave
+// row groups in flight per wave: RowGeom<D>::UNROLL (four up to D = 128, fewer at the wide widths)
 
 template <int D>
 struct Row {
@@ -74,6 +75,7 @@ __global__ __launch_bounds__(kBlock) void bpr_fwd_bwd_kernel(
     float* __restrict__ gradU, float* __restrict__ gradI,
     float* __restrict__ loss_partials, int32_t* __restrict__ err_flag, uint8_t* __restrict__ touched) {
   using G = RowGeom<D>;
+  constexpr int kUnroll = G::UNROLL;
   constexpr int PER_WAVE = TILE / kWavesPerBlock;
   __shared__ int32_t s_idx[3][TILE];
   __shared__ float s_red[kWavesPerBlock];
@@ -170,6 +172,7 @@ __global__ __launch_bounds__(kBlock) void mf_score_kernel(
     int64_t B, int64_t num_users, int64_t num_items,
     float* __restrict__ out, int32_t* __restrict__ err_flag) {
   using G = RowGeom<D>;
+  constexpr int kUnroll = G::UNROLL;
   __shared__ int32_t s_idx[2][kTile];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   const int sub = lane / G::LPR, l = lane % G::LPR;
@@ -217,6 +220,7 @@ __global__ __launch_bounds__(kBlock) void mf_score_backward_kernel(
     const float* __restrict__ gout, int64_t B, int64_t num_users, int64_t num_items,
     float* __restrict__ gradU, float* __restrict__ gradI, int32_t* __restrict__ err_flag) {
   using G = RowGeom<D>;
+  constexpr int kUnroll = G::UNROLL;
   __shared__ int32_t s_idx[2][kTile];
   __shared__ float s_g[kTile];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -282,6 +286,9 @@ using namespace yr;
     case 32: { constexpr int kD = 32; __VA_ARGS__; } break;   \
     case 64: { constexpr int kD = 64; __VA_ARGS__; } break;   \
     case 128: { constexpr int kD = 128; __VA_ARGS__; } break; \
+    case 256: { constexpr int kD = 256; __VA_ARGS__; } break; \
+    case 512: { constexpr int kD = 512; __VA_ARGS__; } break; \
+    case 1024: { constexpr int kD = 1024; __VA_ARGS__; } break; \
     default: return YR_ERR_UNSUPPORTED;                       \
   }
 
@@ -351,13 +358,6 @@ extern "C" int yr_bpr_mf_fwd_bwd(const float* U, const float* I, const int64_t* 
 // The whole step for small batches in two launches: scatter (above, marking the rows it touches) and
 // one dense Adam pass over BOTH tables that reads / clears a gradient row only where it was marked
 // and reduces the loss partials (csrc/optim.hip).
-extern "C" int yr_adam_dense_dual(float* p0, float* g0, float* m0, float* v0, int64_t n0, float* p1, float* g1,
-                                  float* m1, float* v1, int64_t n1, int row_width, uint8_t* touched0,
-                                  uint8_t* touched1, double lr, double step_size, double bc2_sqrt, double beta1,
-                                  double beta2, double eps, double weight_decay, int mode,
-                                  const float* loss_partials, float loss_scale, float* loss_out, double* loss_accum,
-                                  void* stream);
-
 extern "C" int yr_bpr_mf_scatter_step(float* U, float* I, float* gradU, float* gradI, float* mU, float* vU,
                                       float* mI, float* vI, uint8_t* touched, const int64_t* user,
                                       const int64_t* pos, const int64_t* neg, int64_t B, int D, int64_t num_users,
@@ -366,13 +366,13 @@ extern "C" int yr_bpr_mf_scatter_step(float* U, float* I, float* gradU, float* g
                                       int mode, float* loss_partials, float* loss_out, double* loss_accum,
                                       int32_t* err_flag, void* stream) {
   if (!gradU || !gradI || !mU || !vU || !mI || !vI || !U || !I) return YR_ERR_BADARG;
-  if (D != 16 && D != 32 && D != 64 && D != 128) return YR_ERR_UNSUPPORTED;
+  if (D != 16 && D != 32 && D != 64 && D != 128 && D != 256 && D != 512 && D != 1024) return YR_ERR_UNSUPPORTED;
   const int rc = fwd_bwd_launch(U, I, user, pos, neg, B, D, num_users, num_items, inv_batch, gradU, gradI,
                                 loss_partials, err_flag, touched, stream);
   if (rc) return rc;
-  return yr_adam_dense_dual(U, gradU, mU, vU, num_users * D, I, gradI, mI, vI, num_items * D, D, touched,
-                            touched ? touched + num_users : nullptr, lr, step_size, bc2_sqrt, beta1, beta2, eps,
-                            weight_decay, mode, loss_partials, inv_batch, loss_out, loss_accum, stream);
+  return adam_dense_dual_launch(U, gradU, mU, vU, num_users * D, I, gradI, mI, vI, num_items * D, D, touched,
+                                touched ? touched + num_users : nullptr, lr, step_size, bc2_sqrt, beta1, beta2, eps,
+                                weight_decay, mode, loss_partials, inv_batch, loss_out, loss_accum, stream, true);
 }
 
 extern "C" int yr_loss_finalize(const float* loss_partials, float scale, float* loss_out, double* loss_accum,

@@ -21,10 +21,15 @@ constexpr int kListParts = 32;
 // atomics run at full rate for: 256 contiguous bytes or two 128-B segments).
 template <int D>
 struct RowGeom {
-  static_assert(D == 16 || D == 32 || D == 64 || D == 128, "unsupported width");
+  static_assert(D == 16 || D == 32 || D == 64 || D == 128 || D == 256 || D == 512 || D == 1024, "unsupported width");
   static constexpr int LPR = D < 64 ? D : 64;   // lanes per row
-  static constexpr int EPL = D / LPR;           // elements per lane (1 or 2)
+  static constexpr int EPL = D / LPR;           // elements per lane (1 or 2; 4, 8, 16 at the wide widths 256 .. 1024)
   static constexpr int RPW = kWave / LPR;       // rows per wave pass
+  // Row groups a wave keeps in flight in the push-form kernels (csrc/bpr_mf.hip).  bpr_fwd_bwd_kernel holds three
+  // rows per group: 3 x UNROLL x EPL registers.  Four groups up to EPL = 2; above, the depth that keeps every wide
+  // instantiation free of scratch and under 96 VGPRs — 24 / 24 / 48 row registers at D = 256 / 512 / 1024 (compiled
+  // counts in DESIGN 4.9).
+  static constexpr int UNROLL = EPL <= 2 ? 4 : EPL == 4 ? 2 : 1;
 };
 
 // sum over the LPR lanes of a row group; every lane of the group gets the total

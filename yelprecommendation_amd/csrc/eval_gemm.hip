@@ -88,6 +88,84 @@ __global__ __launch_bounds__(kBlock) void mf_scores_mfma_kernel(const float* __r
   }
 }
 
+// The wide widths (D = 256, 512, 1,024): K no longer fits in registers, so the same block walks D in slabs of 128
+// dims.  The four 32 x 32 accumulators of a wave stay live across the slabs (one f32 accumulator per score: D
+// products, fma-chained, as above); per slab the 128 item rows' slab is staged in LDS and the lane's half (64 dims)
+// of its user's slab is loaded from global memory (L2: 128 users x D x 4 B per workgroup).
+constexpr int kEvalSlab = 128;
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void mf_scores_mfma_wide_kernel(const float* __restrict__ U,
+                                                                     const float* __restrict__ I,
+                                                                     const int64_t* __restrict__ users, int64_t nrows,
+                                                                     int64_t num_users, int64_t num_items,
+                                                                     float* __restrict__ S, int64_t row_stride,
+                                                                     int32_t* __restrict__ err_flag) {
+  static_assert(D % kEvalSlab == 0 && D > kEvalSlab, "wide widths only");
+  constexpr int SD = kEvalSlab, HALF = SD / 2, PITCH = SD + 4;
+  __shared__ __attribute__((aligned(16))) float s_items[kEvalItems * PITCH];
+
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int i = lane & 31, h = lane >> 5;
+  const int64_t row0 = (int64_t)blockIdx.y * kEvalUsers;
+  const int64_t item0 = (int64_t)blockIdx.x * kEvalItems;
+
+  const int64_t r = row0 + wave * 32 + i;
+  int64_t uid = r < nrows ? users[r] : 0;
+  bool ok = r < nrows;
+  if (ok && (uint64_t)uid >= (uint64_t)num_users) {
+    if (err_flag) atomicOr(err_flag, YR_FLAG_BAD_USER);
+    ok = false;
+    uid = 0;
+  }
+
+  f32x16 acc[kEvalItems / 32];
+#pragma unroll
+  for (int t = 0; t < kEvalItems / 32; ++t) acc[t] = zero16();
+
+#pragma unroll 1
+  for (int sl = 0; sl < D / SD; ++sl) {
+    if (sl > 0) __syncthreads();                   // everyone is done with the previous slab
+    for (int q = threadIdx.x; q < kEvalItems * (SD / 4); q += kBlock) {
+      const int rr = q / (SD / 4), c = q % (SD / 4);
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (item0 + rr < num_items) v = *reinterpret_cast<const float4*>(I + (item0 + rr) * D + sl * SD + 4 * c);
+      *reinterpret_cast<float4*>(s_items + rr * PITCH + 4 * c) = v;
+    }
+    float a[HALF];
+#pragma unroll
+    for (int q = 0; q < HALF / 4; ++q) {
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (ok) v = *reinterpret_cast<const float4*>(U + uid * D + sl * SD + h * HALF + 4 * q);
+      a[4 * q + 0] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < kEvalItems / 32; ++t) {
+      const float* src = s_items + (t * 32 + i) * PITCH + h * HALF;
+#pragma unroll
+      for (int q = 0; q < HALF / 4; ++q) {
+        const float4 v = *reinterpret_cast<const float4*>(src + 4 * q);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * q + 0], v.x, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * q + 1], v.y, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * q + 2], v.z, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[4 * q + 3], v.w, acc[t], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < kEvalItems / 32; ++t) {
+    const int64_t col = item0 + t * 32 + i;
+    if (col < num_items) {
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int64_t row = row0 + wave * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+        if (row < nrows) S[row * row_stride + col] = acc[t][reg];
+      }
+    }
+  }
+}
+
 }  // namespace yr
 
 using namespace yr;
@@ -107,6 +185,9 @@ extern "C" int yr_mf_scores_gemm(const float* U, const float* I, const int64_t* 
     case 32: hipLaunchKernelGGL((mf_scores_mfma_kernel<32>), grid, dim3(kBlock), 0, s, U, I, users, nrows, num_users, num_items, scores, row_stride, err_flag); break;
     case 64: hipLaunchKernelGGL((mf_scores_mfma_kernel<64>), grid, dim3(kBlock), 0, s, U, I, users, nrows, num_users, num_items, scores, row_stride, err_flag); break;
     case 128: hipLaunchKernelGGL((mf_scores_mfma_kernel<128>), grid, dim3(kBlock), 0, s, U, I, users, nrows, num_users, num_items, scores, row_stride, err_flag); break;
+    case 256: hipLaunchKernelGGL((mf_scores_mfma_wide_kernel<256>), grid, dim3(kBlock), 0, s, U, I, users, nrows, num_users, num_items, scores, row_stride, err_flag); break;
+    case 512: hipLaunchKernelGGL((mf_scores_mfma_wide_kernel<512>), grid, dim3(kBlock), 0, s, U, I, users, nrows, num_users, num_items, scores, row_stride, err_flag); break;
+    case 1024: hipLaunchKernelGGL((mf_scores_mfma_wide_kernel<1024>), grid, dim3(kBlock), 0, s, U, I, users, nrows, num_users, num_items, scores, row_stride, err_flag); break;
     default: return YR_ERR_UNSUPPORTED;
   }
   return launch_status();

@@ -153,6 +153,15 @@ __global__ __launch_bounds__(kBlock) void et_split_rows_kernel(const float* __re
 // Sixteen lanes per row, D / 16 floats of the rows each.  Lane l owns hint l: its binary search in the row's masked
 // ids and its repeated-id test run once (not once per lane), the k dot products are shared work (47 us with every
 // lane doing everything, hint after hint; 56 us with the k searches of a lane interleaved).
+// The margin, as a multiple of A.  An f32 sum of D products and the bias, in any order, is off its exact value by at
+// most (D + 1) 2^-24 A to first order (every term passes through at most D + 1 roundings); the split form adds what
+// its three-term operands and six-of-nine partial products drop, below 2^-24 A in all.  Two such computations (this
+// kernel's and the sweep's) can therefore differ by 2 (D + 2) 2^-24 A.  D = 64: 7.9e-6 A (3.9e-6 A each); 1.6e-5 is
+// that with a factor two to spare, kept as it is up to D = 128 (1.55e-5 A).  The wide widths take the same
+// expression with the first-order terms' slack: 2.18 (D + 2) 2^-24 = 1.3e-7 (D + 2) — 3.4e-5, 6.7e-5 and 1.33e-4
+// at D = 256, 512 and 1,024.  (Too small a margin would cost correctness; too large only candidates.)
+__host__ __device__ constexpr float et_hint_margin(int D) { return D <= 128 ? 1.6e-5f : 1.3e-7f * (float)(D + 2); }
+
 template <int D>
 __global__ __launch_bounds__(kBlock) void et_hint_bound_kernel(
     const float* __restrict__ U, const float* __restrict__ I, const float* __restrict__ item_bias,
@@ -165,9 +174,12 @@ __global__ __launch_bounds__(kBlock) void et_hint_bound_kernel(
   const int64_t r = row < nrows ? row : nrows - 1;   // every lane group runs everything (shuffles below)
   const int64_t uid = users[r];
   const bool user_ok = (uint64_t)uid < (uint64_t)num_users;
-  float uu[C];
+  constexpr bool WIDE = D > 128;                     // the user's row stays in memory, the dot product is a loop
+  float uu[WIDE ? 1 : C];
+  if constexpr (!WIDE) {
 #pragma unroll
-  for (int c = 0; c < C; ++c) uu[c] = user_ok ? U[uid * D + C * l + c] : 0.0f;
+    for (int c = 0; c < C; ++c) uu[c] = user_ok ? U[uid * D + C * l + c] : 0.0f;
+  }
   const int64_t m_lo = mask_ptr ? mask_ptr[r] : 0;
   const int len = mask_ptr ? (int)(mask_ptr[r + 1] - m_lo) : 0;
   const int64_t* mrow = mask_idx + m_lo;
@@ -196,7 +208,19 @@ __global__ __launch_bounds__(kBlock) void et_hint_bound_kernel(
 #pragma unroll
     for (int t = 0; t < HPL; ++t) fine = fine && !(j < l + G * t && l + G * t < k && idj == my[t]);
     float s = 0.0f, a = 0.0f;
-    if (idj >= 0) {
+    if constexpr (WIDE) {
+      if (idj >= 0 && user_ok) {
+        const float* urow = U + uid * D + C * l;
+        const float* irow = I + (int64_t)idj * D + C * l;
+#pragma unroll 4
+        for (int c = 0; c < C; c += 4) {
+          const float4 u4 = ld4(urow + c), i4 = ld4(irow + c);
+          const float x0 = u4.x * i4.x, x1 = u4.y * i4.y, x2 = u4.z * i4.z, x3 = u4.w * i4.w;
+          s += x0; s += x1; s += x2; s += x3;
+          a += fabsf(x0); a += fabsf(x1); a += fabsf(x2); a += fabsf(x3);
+        }
+      }
+    } else if (idj >= 0) {
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         const float x = uu[c] * I[(int64_t)idj * D + C * l + c];
@@ -218,7 +242,7 @@ __global__ __launch_bounds__(kBlock) void et_hint_bound_kernel(
   for (int t = 0; t < HPL; ++t) {
     const float b = item_bias && my[t] >= 0 ? item_bias[my[t]] : 0.0f;
     if (l + G * t < k) {
-      const float e = masked[t] ? mask_value : (mys[t] + b) - 1.6e-5f * (mya[t] + fabsf(b));
+      const float e = masked[t] ? mask_value : (mys[t] + b) - et_hint_margin(D) * (mya[t] + fabsf(b));
       fine = fine && e == e;                         // a NaN score proves nothing (fminf would drop it silently)
       eff = fminf(eff, e);
     }
@@ -1019,6 +1043,234 @@ __global__ __launch_bounds__(kPpThreads) void mf_eval_topk_pp_kernel(
   et_finish_lists<KK>(Ls, Li, k, h, row, nrows, partial, out);
 }
 
+// ---- the sweep for WIDE rows (D = 256, 512, 1,024) -------------------------------------------------------------------
+// A user's row no longer fits in registers as the B operand, so D is walked in slabs of 128 dims (64 in the split form).  Per group
+// of TILES 32-item tiles (one 32 x 32 accumulator each, live across the slabs: one f32 accumulator per score, started
+// from the item bias, D products in it — the arithmetic of the narrow forms) and per slab:
+//   * the group's item rows' slab is staged in LDS (f32 rows, or the three bf16 planes of et_split_rows_kernel: the
+//     planes table is generic in D, a slab is 128 contiguous bytes of each plane);
+//   * every lane loads ITS user's slab fragment from global memory (L2: 128 users x D x 4 B per workgroup; split into
+//     three bf16 terms in registers in the split form) — amortised over the TILES tiles;
+//   * the slab's matrix instructions go into each of the TILES accumulators, in the narrow kernels' order.
+// After the last slab lane (i, h) holds its own user's scores for 16 items of each tile, the shape the narrow forms'
+// selection consumes: the same mask cursor, candidate buffers, lockstep flush (et_bubble), early-out, list start
+// (hint thresholds), half-wave merge and slice merge.  Catalogue slices are cut by the same rule (et_slices).
+// One stage buffer (two barriers per slab): with two workgroups per CU the other workgroup's matrix instructions
+// cover the staging.  This form NEVER runs a prescan: YR_EVAL_FORCE_PRESCAN / YR_EVAL_NO_PRESCAN are accepted and
+// change nothing; YR_EVAL_TWO_ROLES / YR_EVAL_FOUR_WAVES likewise (one wide form).
+constexpr int kEwSlab = 128;
+constexpr int kEwSlabSplit = 64;       // split form: the slab's user fragment is 3 x 4 x 4 registers of bf16 planes
+constexpr int kEwTiles = 2;
+
+template <int D, int KK, bool BIAS, bool SPLIT>
+__global__ __launch_bounds__(kEtThreads, 2) void mf_eval_topk_wide_kernel(
+    const float* __restrict__ U, const void* __restrict__ I_any, const float* __restrict__ item_bias,
+    const int64_t* __restrict__ users, int64_t nrows, int64_t num_users, int num_items,
+    const int64_t* __restrict__ mask_ptr, const int64_t* __restrict__ mask_idx, float mask_value, int k,
+    int64_t* __restrict__ out, TopEntry* __restrict__ partial, int items_per_slice, const float* __restrict__ row_tau,
+    int32_t* __restrict__ err_flag) {
+  static_assert(D % kEwSlab == 0 && D > kEwSlab, "wide widths only");
+  constexpr int SD = SPLIT ? kEwSlabSplit : kEwSlab, NS = D / SD, TILES = kEwTiles, MT = 32 * TILES;
+  constexpr int HALF = SD / 2;                          // f32: dims of the slab per lane
+  constexpr int KB = SD / 16;                           // SPLIT: 16-deep blocks per slab
+  constexpr int ROWB = SPLIT ? 6 * SD + 16 : 4 * (SD + 4);   // an odd number of 16-byte units, as in the narrow forms
+  constexpr int ROW16 = SPLIT ? 3 * SD / 8 : SD / 4;    // 16-byte units of payload per item and slab
+  constexpr int GROW16 = SPLIT ? 3 * D / 8 : D / 4;     // 16-byte units per item in global memory
+  constexpr int NV = MT * ROW16 / kEtThreads;
+  static_assert(MT * ROW16 % kEtThreads == 0, "units per thread");
+  constexpr int BUFCAP = kEtFlushAt + kEtCheckEvery;
+  __shared__ __attribute__((aligned(16))) unsigned char s_items[MT * ROWB];
+  __shared__ TopEntry s_buf[BUFCAP][kEtThreads];
+  __shared__ __attribute__((aligned(16))) float s_bias[BIAS ? MT : 4];
+  const uint4* __restrict__ I16 = static_cast<const uint4*>(I_any);
+
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int i = lane & 31, h = lane >> 5;
+  const int64_t row = (int64_t)blockIdx.x * kEtUsers + wave * kEtUsersPerWave + i;
+  const int item_lo = blockIdx.y * items_per_slice;
+  const int item_hi = min(num_items, item_lo + items_per_slice);
+
+  int64_t uid;
+  const bool ok = et_row_user(users, row, nrows, num_users, err_flag, uid);
+  const float* __restrict__ urow = U + (ok ? uid : 0) * D;
+
+  float Ls[KK];
+  int32_t Li[KK];
+  const float tau0 = et_start_lists<KK>(Ls, Li, k, ok, row, row_tau, nullptr, 0);
+  float tau = fmaxf(Ls[KK - 1], tau0);
+  int cnt = 0;
+  const bool lazy_mask = mask_value <= -3.0e38f;     // uniform
+  int64_t m_cur = 0, m_end = 0;
+  int next_masked = 0x7fffffff, after_next = 0x7fffffff;
+  if (mask_ptr && row < nrows) {
+    m_cur = mask_ptr[row];
+    m_end = mask_ptr[row + 1];
+    while (m_cur < m_end && mask_idx[m_cur] < item_lo) ++m_cur;   // masks below this slice
+    if (m_cur < m_end) next_masked = (int)mask_idx[m_cur];
+    if (m_cur + 1 < m_end) after_next = (int)mask_idx[m_cur + 1];
+  }
+
+  auto flush = [&]() {
+    for (int j = 0; __ballot(j < cnt) != 0ull; ++j) {              // wave-uniform trip count
+      const bool live = j < cnt;
+      const float cs = s_buf[j][threadIdx.x].s;
+      const int32_t ci = s_buf[j][threadIdx.x].i;
+      et_bubble<KK>(Ls, Li, cs, ci, live);
+    }
+    cnt = 0;
+    tau = fmaxf(Ls[KK - 1], tau0);
+  };
+
+  // slab `sl` of the MT item rows from c0 on: global -> LDS (zeros beyond the slice); the bias with slab 0
+  auto stage = [&](int c0, int sl) {
+    if (BIAS && sl == 0 && threadIdx.x < MT)
+      s_bias[threadIdx.x] = c0 + (int)threadIdx.x < item_hi ? item_bias[c0 + threadIdx.x] : 0.0f;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int q = threadIdx.x + v * kEtThreads;
+      const int r = q / ROW16, c = q % ROW16;
+      // SPLIT: plane c / (SD / 8) of the row, unit c % (SD / 8) of the plane's slab
+      const int g = SPLIT ? (c / (SD / 8)) * (D / 8) + sl * (SD / 8) + c % (SD / 8) : sl * (SD / 4) + c;
+      uint4 x = make_uint4(0u, 0u, 0u, 0u);
+      if (c0 + r < item_hi) x = I16[(int64_t)(c0 + r) * GROW16 + g];
+      *reinterpret_cast<uint4*>(s_items + r * ROWB + 16 * c) = x;
+    }
+  };
+
+  // mask, tail, threshold test and candidates of one tile: the epilogue of mf_eval_topk_kernel
+  auto select = [&](f32x16& acc, int item0) {
+    uint32_t bits = 0;
+    while (next_masked < item0 + 32) {
+      if (next_masked >= item0) bits |= 1u << (next_masked - item0);
+      ++m_cur;
+      next_masked = after_next;
+      after_next = m_cur + 1 < m_end ? (int)mask_idx[m_cur + 1] : 0x7fffffff;
+    }
+    const uint32_t mine = bits >> (4 * h);
+    if (!lazy_mask && __ballot(bits != 0) != 0ull) {
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg)
+        if ((mine >> ((reg & 3) + 8 * (reg >> 2))) & 1u) acc[reg] = mask_value;
+    }
+    if (item0 + 32 > item_hi) {                      // wave-uniform: last, partial tile of the slice
+      const uint32_t beyond = (~0u << (item_hi - item0)) >> (4 * h);
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg)
+        if ((beyond >> ((reg & 3) + 8 * (reg >> 2))) & 1u) acc[reg] = -INFINITY;   // not an item
+    }
+    bool scan = true;
+#if YR_ET_EARLY_OUT
+    if (row_tau) {                                   // wave-uniform
+      float mx = acc[0];
+#pragma unroll
+      for (int reg = 1; reg < 16; ++reg) mx = fmaxf(mx, acc[reg]);
+      scan = __ballot(mx > tau) != 0ull;
+    }
+#endif
+    if (scan)
+#pragma unroll
+    for (int part = 0; part < 16 / kEtCheckEvery; ++part) {
+#pragma unroll
+      for (int q = 0; q < kEtCheckEvery; ++q) {
+        const int reg = part * kEtCheckEvery + q;
+        float sc = acc[reg];
+        if (sc > tau) {
+          if (lazy_mask && ((mine >> ((reg & 3) + 8 * (reg >> 2))) & 1u)) sc = mask_value;
+          if (sc > tau) {
+            TopEntry c;
+            c.s = sc;
+            c.i = item0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            s_buf[cnt][threadIdx.x] = c;
+            ++cnt;
+          }
+        }
+      }
+      if (__ballot(cnt > kEtFlushAt) != 0ull) flush();
+    }
+  };
+
+#pragma unroll 1
+  for (int c0 = item_lo; c0 < item_hi; c0 += MT) {
+    f32x16 acc[TILES];
+#pragma unroll 1
+    for (int sl = 0; sl < NS; ++sl) {
+      __syncthreads();                               // everyone is done reading the previous slab (and its bias)
+      stage(c0, sl);
+      // B operand of this slab: f32 dims [sl SD + h SD/2, + SD/2); SPLIT dims sl SD + 16 kb + 8 h + j, three planes
+      float ub[SPLIT ? 1 : HALF];
+      uint4 us[3][KB];                               // (unused, and removed by the compiler, in the f32 form)
+      if constexpr (SPLIT) {
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+          float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+          if (ok) {
+            lo = *reinterpret_cast<const float4*>(urow + sl * SD + 16 * kb + 8 * h);
+            hi = *reinterpret_cast<const float4*>(urow + sl * SD + 16 * kb + 8 * h + 4);
+          }
+          et_split3x8(lo, hi, us[0][kb], us[1][kb], us[2][kb]);
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < HALF / 4; ++q) {
+          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (ok) v = *reinterpret_cast<const float4*>(urow + sl * SD + h * HALF + 4 * q);
+          ub[4 * q + 0] = v.x; ub[4 * q + 1] = v.y; ub[4 * q + 2] = v.z; ub[4 * q + 3] = v.w;
+        }
+      }
+      __syncthreads();
+      if (sl == 0) {
+#pragma unroll
+        for (int t = 0; t < TILES; ++t) {
+          acc[t] = zero16();
+          if (BIAS) {                                // accumulator register 4 g + j holds item 8 g + 4 h + j of the tile
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              const float4 b4 = *reinterpret_cast<const float4*>(&s_bias[t * 32 + 8 * g + 4 * h]);
+              acc[t][4 * g + 0] = b4.x; acc[t][4 * g + 1] = b4.y; acc[t][4 * g + 2] = b4.z; acc[t][4 * g + 3] = b4.w;
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) {
+        if constexpr (SPLIT) {
+          const unsigned char* src = s_items + (t * 32 + i) * ROWB + 16 * h;
+#pragma unroll
+          for (int kb = 0; kb < KB; ++kb) {
+            const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(src + 32 * kb);
+            const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(src + 2 * SD + 32 * kb);
+            const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(src + 4 * SD + 32 * kb);
+            const bf16x8 u1 = __builtin_bit_cast(bf16x8, us[0][kb]);
+            const bf16x8 u2 = __builtin_bit_cast(bf16x8, us[1][kb]);
+            const bf16x8 u3 = __builtin_bit_cast(bf16x8, us[2][kb]);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, u1, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u3, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, u2, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, u1, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u2, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u1, acc[t], 0, 0, 0);
+          }
+        } else {
+          const float* src = reinterpret_cast<const float*>(s_items) + (t * 32 + i) * (SD + 4) + h * HALF;
+#pragma unroll
+          for (int q = 0; q < HALF / 4; ++q) {
+            const float4 b = *reinterpret_cast<const float4*>(src + 4 * q);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.x, ub[4 * q + 0], acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.y, ub[4 * q + 1], acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.z, ub[4 * q + 2], acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.w, ub[4 * q + 3], acc[t], 0, 0, 0);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < TILES; ++t)
+      if (c0 + 32 * t < item_hi) select(acc[t], c0 + 32 * t);   // wave-uniform
+  }
+  flush();
+  et_finish_lists<KK>(Ls, Li, k, h, row, nrows, partial, out);
+}
+
 // out[r, :] = the k best of the S sorted partial lists of row r (score descending, item ascending
 // among equal scores; empty slots carry item 0x7fffffff and lose every comparison).  One thread per
 // row: S cursors, k rounds.
@@ -1114,7 +1366,8 @@ static bool et_mode_ok(int mode) {
          (mode & (YR_EVAL_TWO_ROLES | YR_EVAL_FOUR_WAVES)) != (YR_EVAL_TWO_ROLES | YR_EVAL_FOUR_WAVES) &&
          (mode & (YR_EVAL_NO_PRESCAN | YR_EVAL_FORCE_PRESCAN)) != (YR_EVAL_NO_PRESCAN | YR_EVAL_FORCE_PRESCAN);
 }
-static bool et_dim_ok(int D) { return D == 16 || D == 32 || D == 64 || D == 128; }
+static bool et_dim_wide(int D) { return D == 256 || D == 512 || D == 1024; }
+static bool et_dim_ok(int D) { return D == 16 || D == 32 || D == 64 || D == 128 || et_dim_wide(D); }
 
 extern "C" int64_t yr_mf_eval_topk_planes_bytes(int64_t num_items, int D) {
   if (num_items <= 0 || !et_dim_ok(D)) return YR_ERR_BADARG;
@@ -1125,7 +1378,7 @@ extern "C" int64_t yr_mf_eval_topk_workspace_bytes(int64_t nrows, int64_t num_it
   if (nrows < 0 || num_items <= 0 || k <= 0 || k > kEtMaxK || !et_mode_ok(mode) || !et_dim_ok(D)) return YR_ERR_BADARG;
   const int S = et_slices(nrows, num_items);
   return ((mode & YR_EVAL_BF16X3) ? et_plane_bytes(num_items, D) : 0) + et_tau_bytes(nrows) +
-         (et_prescan_wanted(num_items, k, mode) ? et_gmax_bytes(nrows, S) : 0) +
+         (et_prescan_wanted(num_items, k, mode) && !et_dim_wide(D) ? et_gmax_bytes(nrows, S) : 0) +   // (no wide prescan)
          (S > 1 ? nrows * S * k * (int64_t)sizeof(TopEntry) : 0);
 }
 
@@ -1199,6 +1452,30 @@ void et_launch_d(const EtArgs& a, bool split, hipStream_t s) {
     else et_launch<DD, false, false>(a, s);
   }
 }
+
+template <int DD, bool BB, bool SS>
+void et_launch_wide(const EtArgs& a, hipStream_t s) {
+  const dim3 grid(a.row_blocks, a.slices);
+#define YR_ET_WIDE(KK)                                                                                              \
+  hipLaunchKernelGGL((mf_eval_topk_wide_kernel<DD, KK, BB, SS>), grid, dim3(kEtThreads), 0, s, a.U, a.items,         \
+                     a.item_bias, a.users, a.nrows, a.num_users, a.num_items, a.mask_ptr, a.mask_idx, a.mask_value,  \
+                     a.k, a.out, a.partial, a.per, a.row_tau, a.err_flag)
+  if (a.k <= 4) YR_ET_WIDE(4);
+  else if (a.k <= 10) YR_ET_WIDE(10);
+  else YR_ET_WIDE(16);                                 // (k > 16: refused by the caller)
+#undef YR_ET_WIDE
+}
+
+template <int DD>
+void et_launch_wide_d(const EtArgs& a, bool split, hipStream_t s) {
+  if (a.item_bias) {
+    if (split) et_launch_wide<DD, true, true>(a, s);
+    else et_launch_wide<DD, true, false>(a, s);
+  } else {
+    if (split) et_launch_wide<DD, false, true>(a, s);
+    else et_launch_wide<DD, false, false>(a, s);
+  }
+}
 }  // namespace
 
 extern "C" int yr_mf_eval_topk_bias(const float* U, const float* I, const float* item_bias, const int64_t* users,
@@ -1240,20 +1517,23 @@ extern "C" int yr_mf_eval_topk_bias(const float* U, const float* I, const float*
       case 16: YR_ET_HINT(16); break;
       case 32: YR_ET_HINT(32); break;
       case 64: YR_ET_HINT(64); break;
-      default: YR_ET_HINT(128); break;
+      case 128: YR_ET_HINT(128); break;
+      case 256: YR_ET_HINT(256); break;
+      case 512: YR_ET_HINT(512); break;
+      default: YR_ET_HINT(1024); break;
     }
 #undef YR_ET_HINT
     a.row_tau = tau;
     ws += et_tau_bytes(nrows);
     workspace_bytes -= et_tau_bytes(nrows);
   }
-  if (!a.row_tau && et_prescan_wanted(num_items, k, mode) && workspace_bytes >= et_gmax_bytes(nrows, S)) {   // no room: no prescan
+  if (!a.row_tau && !et_dim_wide(D) && et_prescan_wanted(num_items, k, mode) && workspace_bytes >= et_gmax_bytes(nrows, S)) {   // no room: no prescan
     a.gmax = reinterpret_cast<float*>(ws);
     a.parts = S;
     ws += et_gmax_bytes(nrows, S);
     workspace_bytes -= et_gmax_bytes(nrows, S);
   }
-  const bool two_roles = et_pp_wanted(nrows, D, k, mode, a.row_tau != nullptr);
+  const bool two_roles = !et_dim_wide(D) && et_pp_wanted(nrows, D, k, mode, a.row_tau != nullptr);
   if (two_roles) S = std::min(S, et_pp_slices(nrows, num_items));                          // (the prescan keeps its parts)
   if (S > 1 && workspace_bytes < nrows * S * k * (int64_t)sizeof(TopEntry)) S = 1;          // no room: one slice
   int per = (int)((num_items + S - 1) / S);
@@ -1279,7 +1559,10 @@ extern "C" int yr_mf_eval_topk_bias(const float* U, const float* I, const float*
     case 16: et_launch_d<16>(a, split, s); break;
     case 32: et_launch_d<32>(a, split, s); break;
     case 64: et_launch_d<64>(a, split, s); break;
-    default: et_launch_d<128>(a, split, s); break;
+    case 128: et_launch_d<128>(a, split, s); break;
+    case 256: et_launch_wide_d<256>(a, split, s); break;
+    case 512: et_launch_wide_d<512>(a, split, s); break;
+    default: et_launch_wide_d<1024>(a, split, s); break;
   }
   if (S > 1)
     hipLaunchKernelGGL(mf_eval_merge_kernel, dim3((unsigned)((nrows + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,

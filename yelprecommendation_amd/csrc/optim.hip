@@ -96,6 +96,62 @@ __global__ __launch_bounds__(kBlock) void adam_dual_kernel(DualAdam t, AdamScala
   }
 }
 
+// The same for marked rows of MORE than 64 float4 (row_width 512 and 1,024: two and four waves per row).  A row of
+// row4 <= kBlock consecutive float4, aligned to its own size, lies inside one workgroup iteration of the grid-stride
+// loop (both tables hold whole rows, so the second table starts on a row boundary too).  Every lane reads its row's
+// mark, the workgroup meets at a barrier, and only then does the row's first lane clear the mark: no lane of the row
+// can still be about to read it.  The loop bound is workgroup-uniform (the barrier is reached by all 256 lanes); lanes
+// beyond the end do nothing else.
+template <bool DECOUPLED>
+__global__ __launch_bounds__(kBlock) void adam_dual_wide_kernel(DualAdam t, AdamScalars c,
+                                                                const float* __restrict__ partials, float loss_scale,
+                                                                float* __restrict__ loss_out,
+                                                                double* __restrict__ loss_accum) {
+  const int64_t total = t.n4_0 + t.n4_1;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t base = (int64_t)blockIdx.x * kBlock; base < total; base += stride) {
+    const int64_t i = base + threadIdx.x;
+    const bool active = i < total;
+    const bool second = i >= t.n4_0;
+    const int64_t j = second ? i - t.n4_0 : i;
+    float4* pp = second ? t.p1 : t.p0;
+    float4* gp = second ? t.g1 : t.g0;
+    float4* mp = second ? t.m1 : t.m0;
+    float4* vp = second ? t.v1 : t.v0;
+    uint8_t* tp = second ? t.touched1 : t.touched0;
+    const int64_t row = j / t.row4;
+    const bool has = active && (tp ? tp[row] != 0 : true);
+    __syncthreads();                              // every lane of every row of this iteration has read its mark
+    if (active) {
+      float4 P = pp[j], M = mp[j], V = vp[j];
+      float4 G = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (has) {
+        G = gp[j];
+        gp[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tp && j % t.row4 == 0) tp[row] = 0;
+      }
+      adam_element(P.x, G.x, M.x, V.x, c, std::bool_constant<DECOUPLED>());
+      adam_element(P.y, G.y, M.y, V.y, c, std::bool_constant<DECOUPLED>());
+      adam_element(P.z, G.z, M.z, V.z, c, std::bool_constant<DECOUPLED>());
+      adam_element(P.w, G.w, M.w, V.w, c, std::bool_constant<DECOUPLED>());
+      pp[j] = P;
+      mp[j] = M;
+      vp[j] = V;
+    }
+  }
+  if (partials && blockIdx.x == 0) {              // fixed-order loss reduction, as in adam_dual_kernel
+    __shared__ float s_red[kWavesPerBlock];
+    float s = 0.0f;
+    for (int i = threadIdx.x; i < YR_LOSS_PARTIALS; i += kBlock) s += partials[i];
+    const float tot = block_sum(s, s_red);
+    if (threadIdx.x == 0) {
+      const float v = tot * loss_scale;
+      if (loss_out) loss_out[0] = v;
+      if (loss_accum) loss_accum[0] += (double)v;
+    }
+  }
+}
+
 // Up to YR_ADAM_MULTI_MAX tensors of any size in ONE launch, 16 bytes per lane (every buffer 16-byte aligned;
 // the 1-3 elements after the last whole float4 of a tensor are done by one lane).  The work is cut into chunks of kBlock float4 that never straddle two tensors,
 // so the tensor a workgroup iteration works on is wave-uniform (its pointers stay in scalar registers).
@@ -235,12 +291,13 @@ extern "C" int yr_adam_dense(float* p, float* g, float* m, float* v, int64_t n, 
   return launch_status();
 }
 
-extern "C" int yr_adam_dense_dual(float* p0, float* g0, float* m0, float* v0, int64_t n0, float* p1, float* g1,
-                                  float* m1, float* v1, int64_t n1, int row_width, uint8_t* touched0,
-                                  uint8_t* touched1, double lr, double step_size, double bc2_sqrt, double beta1,
-                                  double beta2, double eps, double weight_decay, int mode,
-                                  const float* loss_partials, float loss_scale, float* loss_out, double* loss_accum,
-                                  void* stream) {
+// yr_adam_dense_dual; `wide_marks`: marked rows of 512 and 1,024 floats are taken too (yr_bpr_mf_scatter_step at the
+// wide widths — the C entry point keeps its one-wave rule for marks)
+int yr::adam_dense_dual_launch(float* p0, float* g0, float* m0, float* v0, int64_t n0, float* p1, float* g1, float* m1,
+                               float* v1, int64_t n1, int row_width, uint8_t* touched0, uint8_t* touched1, double lr,
+                               double step_size, double bc2_sqrt, double beta1, double beta2, double eps,
+                               double weight_decay, int mode, const float* loss_partials, float loss_scale,
+                               float* loss_out, double* loss_accum, void* stream, bool wide_marks) {
   if (n0 < 0 || n1 < 0 || (n0 & 3) || (n1 & 3)) return YR_ERR_BADARG;
   if (mode != YR_OPT_ADAM && mode != YR_OPT_ADAMW) return YR_ERR_UNSUPPORTED;
   if ((n0 > 0 && (!p0 || !g0 || !m0 || !v0)) || (n1 > 0 && (!p1 || !g1 || !m1 || !v1))) return YR_ERR_BADARG;
@@ -248,9 +305,12 @@ extern "C" int yr_adam_dense_dual(float* p0, float* g0, float* m0, float* v0, in
       !aligned16(m1) || !aligned16(v1))
     return YR_ERR_BADARG;
   // a row's mark is read by all row_width / 4 lanes of the row and cleared by the first of them: the lanes of a
-  // row must sit in ONE wave (row_width / 4 divides 64), as yr_adam_dense_flat requires
-  if ((touched0 || touched1) && (row_width <= 0 || (row_width & 3) || n0 % row_width || n1 % row_width ||
-                                 row_width / 4 > kWave || kWave % (row_width / 4)))
+  // row sit in ONE wave (row_width / 4 divides 64), as yr_adam_dense_flat requires, or — wide_marks, row_width 512
+  // and 1,024 — in one workgroup iteration (row_width / 4 is 128 or 256), ordered by a barrier (adam_dual_wide_kernel)
+  const bool marks = touched0 || touched1;
+  const bool wide_rows = wide_marks && marks && row_width > 0 && row_width / 4 > kWave;
+  if (marks && (row_width <= 0 || (row_width & 3) || n0 % row_width || n1 % row_width ||
+                (wide_rows ? kBlock % (row_width / 4) != 0 : kWave % (row_width / 4) != 0)))
     return YR_ERR_BADARG;
   DualAdam t;
   t.p0 = (float4*)p0; t.g0 = (float4*)g0; t.m0 = (float4*)m0; t.v0 = (float4*)v0;
@@ -262,13 +322,31 @@ extern "C" int yr_adam_dense_dual(float* p0, float* g0, float* m0, float* v0, in
   const int64_t total = t.n4_0 + t.n4_1;
   const int grid = grid_for(total > 0 ? total : 1, kBlock);
   hipStream_t s = (hipStream_t)stream;
-  if (mode == YR_OPT_ADAMW)
+  if (wide_rows) {
+    if (mode == YR_OPT_ADAMW)
+      hipLaunchKernelGGL((adam_dual_wide_kernel<true>), dim3(grid), dim3(kBlock), 0, s, t, c, loss_partials,
+                         loss_scale, loss_out, loss_accum);
+    else
+      hipLaunchKernelGGL((adam_dual_wide_kernel<false>), dim3(grid), dim3(kBlock), 0, s, t, c, loss_partials,
+                         loss_scale, loss_out, loss_accum);
+  } else if (mode == YR_OPT_ADAMW)
     hipLaunchKernelGGL((adam_dual_kernel<true>), dim3(grid), dim3(kBlock), 0, s, t, c, loss_partials, loss_scale,
                        loss_out, loss_accum);
   else
     hipLaunchKernelGGL((adam_dual_kernel<false>), dim3(grid), dim3(kBlock), 0, s, t, c, loss_partials, loss_scale,
                        loss_out, loss_accum);
   return launch_status();
+}
+
+extern "C" int yr_adam_dense_dual(float* p0, float* g0, float* m0, float* v0, int64_t n0, float* p1, float* g1,
+                                  float* m1, float* v1, int64_t n1, int row_width, uint8_t* touched0,
+                                  uint8_t* touched1, double lr, double step_size, double bc2_sqrt, double beta1,
+                                  double beta2, double eps, double weight_decay, int mode,
+                                  const float* loss_partials, float loss_scale, float* loss_out, double* loss_accum,
+                                  void* stream) {
+  return adam_dense_dual_launch(p0, g0, m0, v0, n0, p1, g1, m1, v1, n1, row_width, touched0, touched1, lr, step_size,
+                                bc2_sqrt, beta1, beta2, eps, weight_decay, mode, loss_partials, loss_scale, loss_out,
+                                loss_accum, stream, false);
 }
 
 extern "C" int yr_adam_dense_flat(float* const* p, float* const* g, float* const* m, float* const* v,

@@ -16,6 +16,10 @@ FLAG_BAD_USER, FLAG_BAD_ITEM = 1, 2
 OPT_ADAM, OPT_ADAMW = 0, 1
 PULL_USER_PHASE, PULL_ITEM_PHASE = 1, 2
 SUPPORTED_WIDTHS = (16, 32, 64, 128)
+# BPR-MF alone also takes the wide widths: push-form training (csrc/bpr_mf.hip), the slab sweep of the fused
+# evaluation for k <= 16 (csrc/eval_topk.hip) and the score GEMM.  The pull form stays at SUPPORTED_WIDTHS.
+WIDE_WIDTHS = (256, 512, 1024)
+MF_WIDTHS = SUPPORTED_WIDTHS + WIDE_WIDTHS
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -898,7 +902,8 @@ def sort_mask_rows(mask_ptr, mask_idx):
 
 
 def fused_eval_supports(k, d):
-    """The fused evaluation kernel keeps top-k lists of 4 / 10 / 16 / 32 entries in registers (32: up to D = 64)."""
+    """The fused evaluation kernel keeps top-k lists of 4 / 10 / 16 / 32 entries in registers (32: up to D = 64;
+    the wide widths 256 / 512 / 1024 like D = 128: k <= 16)."""
     return k <= 16 or (k <= 32 and d <= 64)
 
 

@@ -44,6 +44,8 @@ class MatrixFactorization(BaseModel):
 
     def __init__(self, cfg, num_users, num_items):
         super().__init__()
+        if cfg.embed_size not in engine.MF_WIDTHS:
+            raise NotImplementedError(f"MatrixFactorization: embed_size {cfg.embed_size} (the kernels take {engine.MF_WIDTHS})")
         self.user_embedding = nn.Embedding(num_users, cfg.embed_size, dtype=torch.float32)
         self.item_embedding = nn.Embedding(num_items, cfg.embed_size, dtype=torch.float32)
         self._init_weights()
