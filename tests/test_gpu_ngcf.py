@@ -454,8 +454,12 @@ def test_batch_aware_propagation_equals_full_graph_propagation(device, tmp_path,
     (24, 0.5, "adam", 3, 64), (700, 0.5, "adamw", 3, 64), (700, 0.0, "adam", 3, 64), (24, 1e9, "adam", 3, 64),
     # seven layers, the most yr_ngcf_bpr_step takes (K + 1 layer buffers <= YR_NGCF_MAX_LAYERS): 14 weight matrices
     # in the step's one multi-tensor Adam launch
-    (24, 0.5, "adam", 7, 16)],
-    ids=["24-0.5-adam", "700-0.5-adamw", "700-0.0-adam", "24-1000000000.0-adam", "24-0.5-adam-7x16"])
+    (24, 0.5, "adam", 7, 16),
+    # batches of 8190, 8193, ... triplets: across the switch (B > 8192) from the loss finished by its one workgroup to
+    # partials, the clearing of the unused partial slots and yr_loss_finalize
+    (8190, 0.5, "adam", 2, 32)],
+    ids=["24-0.5-adam", "700-0.5-adamw", "700-0.0-adam", "24-1000000000.0-adam", "24-0.5-adam-7x16",
+         "8190-0.5-adam-2x32"])
 def test_fused_step_equals_autograd_route(device, tmp_path, batch, fraction, optimizer, layers, embed):
     """ngcf_step.NGCFStep (yr_ngcf_bpr_step: every launch of the step issued from C) against the autograd route
     (bpr_forward, zero_grad, BPRLoss, backward, optimizer.step) over six steps on changing batches: the same
