@@ -31,6 +31,7 @@
 // Order: score descending, item id ascending among equal scores (csrc/topk_order.h, shared with csrc/topk.hip).
 // Built with -mllvm -amdgpu-mfma-vgpr-form (csrc/Makefile): accumulators in VGPRs.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "topk_order.h"
@@ -59,21 +60,16 @@ constexpr int kEtMaxK = 32;
 #ifndef YR_ET_TARGET_WGS
 #define YR_ET_TARGET_WGS 768
 #endif
-#ifndef YR_ET_EARLY_OUT
-#define YR_ET_EARLY_OUT 1
-#endif
 #ifndef YR_ET_SPLIT_CHUNK
 #define YR_ET_SPLIT_CHUNK 32
-#endif
-// wave priority experiments (YR_ET_PRIO): 0 none; 1 matrix phase high; 2 epilogue high; 3 a fixed level per workgroup
-#ifndef YR_ET_PRIO
-#define YR_ET_PRIO 0
 #endif
 constexpr int kEtFlushAt = YR_ET_FLUSH_AT;             // flush when some lane holds more than this
 constexpr int kEtCheckEvery = YR_ET_CHECK_EVERY;       // ... checked after this many accumulator registers
 
 #ifdef YR_ET_STAMPS
 // -DYR_ET_STAMPS: shader-clock cycles every wave spends per phase (scratch/eval_phases.sh), summed over the waves
+// (the flush phase is stamped inside the kernel's flush lambda, so it counts the final flush after the sweep too:
+// a little more than in the profiles taken before the sweeps shared et_flush)
 __device__ unsigned long long g_et_phase[8];
 #define ET_CLK() clock64()
 #else
@@ -281,7 +277,14 @@ __host__ __device__ constexpr int et_chunk_items(int D, int KK, bool split) {
 // k-th best score over the whole catalogue, and every list of the user (both half-waves, every slice) starts with
 // a threshold just below it instead of -inf.  What the lists then never see could not have ended in the top k.
 // (Hint lists — et_hint_bound_kernel, row_tau — give a bound of the same kind from k rescored items instead.)
-// ---- pieces both forms of the sweep share (forceinline: the lists and planes stay in the callers' registers) ----
+// ---- pieces the three sweeps share (forceinline: lists, planes and accumulators stay in the callers' registers) ----
+// Three kernels sweep the catalogue — mf_eval_topk_kernel (four waves; also the prescan), mf_eval_topk_pp_kernel (two
+// roles per SIMD) and mf_eval_topk_wide_kernel (D = 256 / 512 / 1,024) — and must produce the same lists.  Each keeps
+// its own loops, staging and barriers; what happens to one tile is written ONCE, here: the user operand
+// (et_row_user, et_user_planes, et_user_half), the accumulator's start and the order of the products (et_start_acc,
+// et_products6, et_tile_split, et_tile_f32), the register -> item mapping (et_reg_item, et_set_where), the mask walk
+// (EtMaskCursor), the lists (et_start_lists, et_flush, et_finish_lists) and the four-wave and wide kernels' candidate
+// test (et_collect; the two-role kernel has its own, see there).
 
 // the user id of this lane's row (false: a row beyond the input or a bad id -> flagged, an all-zero operand)
 __device__ __forceinline__ bool et_row_user(const int64_t* __restrict__ users, int64_t row, int64_t nrows,
@@ -295,20 +298,136 @@ __device__ __forceinline__ bool et_row_user(const int64_t* __restrict__ users, i
   return ok;
 }
 
-// B operand of the split form: dims 16 kb + 8 h + j of every 16-deep block kb of the user's row, three bf16 planes
-template <int D>
-__device__ __forceinline__ void et_user_planes(const float* __restrict__ U, int64_t uid, bool ok, int h,
-                                               uint4 (&us)[3][D / 16]) {
+// B operand of the split form: dims 16 kb + 8 h + j of every 16-deep block kb of `urow` (the user's row, or a slab
+// of it), three bf16 planes; zeros where !ok
+template <int KB>
+__device__ __forceinline__ void et_user_planes(const float* __restrict__ urow, bool ok, int h, uint4 (&us)[3][KB]) {
 #pragma unroll
-  for (int kb = 0; kb < D / 16; ++kb) {
+  for (int kb = 0; kb < KB; ++kb) {
     float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
     if (ok) {
-      lo = *reinterpret_cast<const float4*>(U + uid * D + 16 * kb + 8 * h);
-      hi = *reinterpret_cast<const float4*>(U + uid * D + 16 * kb + 8 * h + 4);
+      lo = *reinterpret_cast<const float4*>(urow + 16 * kb + 8 * h);
+      hi = *reinterpret_cast<const float4*>(urow + 16 * kb + 8 * h + 4);
     }
     et_split3x8(lo, hi, us[0][kb], us[1][kb], us[2][kb]);
   }
 }
+
+// B operand of the f32 form: the HALF dims from `src` on (this half-wave's half of the user's row or slab)
+template <int HALF>
+__device__ __forceinline__ void et_user_half(const float* __restrict__ src, bool ok, float (&ub)[HALF]) {
+#pragma unroll
+  for (int q = 0; q < HALF / 4; ++q) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ok) v = *reinterpret_cast<const float4*>(src + 4 * q);
+    ub[4 * q + 0] = v.x; ub[4 * q + 1] = v.y; ub[4 * q + 2] = v.z; ub[4 * q + 3] = v.w;
+  }
+}
+
+// Accumulator register 4 g + j of lane (i, h) holds item 8 g + 4 h + j of the tile: et_reg_item + 4 h.  Bit words
+// over a tile's items (bit r = item item0 + r) are shifted right by 4 h before they meet it.
+__device__ __forceinline__ constexpr int et_reg_item(int reg) { return (reg & 3) + 8 * (reg >> 2); }
+
+// acc[reg] = value where `mine` (a tile's bit word >> 4 h) has the register's item set
+__device__ __forceinline__ void et_set_where(f32x16& acc, uint32_t mine, float value) {
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg)
+    if ((mine >> et_reg_item(reg)) & 1u) acc[reg] = value;
+}
+
+// the accumulator's start: the item bias of the tile whose 32 values begin at `bias` (LDS)
+__device__ __forceinline__ void et_start_acc(f32x16& acc, const float* bias, int h) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const float4 b4 = *reinterpret_cast<const float4*>(bias + 8 * g + 4 * h);
+    acc[4 * g + 0] = b4.x; acc[4 * g + 1] = b4.y; acc[4 * g + 2] = b4.z; acc[4 * g + 3] = b4.w;
+  }
+}
+
+// The six partial products of one 16-deep block (item terms a1..a3, user terms u1..u3), the small terms first:
+// a3 u1, a1 u3, a2 u2, a2 u1, a1 u2, a1 u1.  THIS order, in every form of the sweep, is what makes their scores —
+// and so their lists — identical.  c = from + the six; `from` may be c itself or a constant (a tile's first block).
+__device__ __forceinline__ void et_products6(f32x16& c, const f32x16& from, const bf16x8 a1, const bf16x8 a2,
+                                             const bf16x8 a3, const bf16x8 u1, const bf16x8 u2, const bf16x8 u3) {
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, u1, from, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u3, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, u2, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, u1, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u2, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u1, c, 0, 0, 0);
+}
+
+// acc += <item row, user> over KB 16-deep blocks, split form.  `src`: the lane's item row in LDS + 16 h — dims
+// 16 kb + 8 h + j of block kb, one ds_read_b128 per plane and block, the planes 32 KB bytes apart.
+template <int KB>
+__device__ __forceinline__ void et_tile_split(f32x16& acc, const unsigned char* src, const uint4 (&us)[3][KB]) {
+#pragma unroll
+  for (int kb = 0; kb < KB; ++kb) {
+    const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(src + 32 * kb);
+    const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(src + 32 * KB + 32 * kb);
+    const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(src + 64 * KB + 32 * kb);
+    et_products6(acc, acc, a1, a2, a3, __builtin_bit_cast(bf16x8, us[0][kb]), __builtin_bit_cast(bf16x8, us[1][kb]),
+                 __builtin_bit_cast(bf16x8, us[2][kb]));
+  }
+}
+
+// the same in f32 instructions: `src` the lane's half (HALF dims) of its item row in LDS, `ub` the user's
+template <int HALF>
+__device__ __forceinline__ void et_tile_f32(f32x16& acc, const float* src, const float (&ub)[HALF]) {
+#pragma unroll
+  for (int q = 0; q < HALF / 4; ++q) {
+    const float4 b = *reinterpret_cast<const float4*>(src + 4 * q);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.x, ub[4 * q + 0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.y, ub[4 * q + 1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.z, ub[4 * q + 2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.w, ub[4 * q + 3], acc, 0, 0, 0);
+  }
+}
+
+// A lane's place in its user's mask list (CSR, ids ascending).  The next TWO masked item ids stay in registers: the
+// load that refills the second one is issued a tile (or more) before its value is needed, so the sweep never waits
+// on it.
+struct EtMaskCursor {
+  const int64_t* __restrict__ idx;
+  int64_t cur = 0, end = 0;
+  int next = 0x7fffffff, after = 0x7fffffff;
+
+  __device__ __forceinline__ EtMaskCursor(const int64_t* __restrict__ mask_ptr, const int64_t* __restrict__ mask_idx,
+                                          int64_t row, int64_t nrows, int item_lo) : idx(mask_idx) {
+    if (mask_ptr && row < nrows) {
+      cur = mask_ptr[row];
+      end = mask_ptr[row + 1];
+      while (cur < end && idx[cur] < item_lo) ++cur;   // masks below this slice
+      if (cur < end) next = (int)idx[cur];
+      if (cur + 1 < end) after = (int)idx[cur + 1];
+    }
+  }
+  // the masked items among [item0, item0 + SPAN), SPAN = 32 or 64: bit r = item item0 + r.  Spans ascend.
+  template <int SPAN>
+  __device__ __forceinline__ auto walk(int item0) {
+    static_assert(SPAN == 32 || SPAN == 64, "one bit word");
+    std::conditional_t<SPAN == 64, uint64_t, uint32_t> bits = 0;
+    while (next < item0 + SPAN) {
+      if (next >= item0) bits |= decltype(bits)(1) << (next - item0);
+      ++cur;
+      next = after;
+      after = cur + 1 < end ? (int)idx[cur + 1] : 0x7fffffff;
+    }
+    return bits;
+  }
+  // a sweep that skips most of the catalogue (the prescan's sample): over the entries below item0 eight at a time
+  // (walk() is one dependent load per entry)
+  __device__ __forceinline__ void skip_to(int item0) {
+    if (next < item0) {
+      const int64_t before = cur;
+      while (cur + 8 < end && (int)idx[cur + 8] < item0) cur += 8;
+      if (cur != before) {
+        next = (int)idx[cur];
+        after = cur + 1 < end ? (int)idx[cur + 1] : 0x7fffffff;
+      }
+    }
+  }
+};
 
 // The private list's start and the floor of its threshold.  Only the top k leave the kernel: the first KK - k places
 // are held by phantom entries (+inf, no item), so the list's last score — the threshold — is the lane's k-th best,
@@ -383,6 +502,62 @@ __device__ __forceinline__ void et_finish_lists(float (&Ls)[KK], int32_t (&Li)[K
   }
 }
 
+// The wave's lockstep flush: slot j of all 64 candidate buffers into the 64 private lists, then the new threshold
+template <int KK, int CAP, int NT>
+__device__ __forceinline__ void et_flush(float (&Ls)[KK], int32_t (&Li)[KK], const TopEntry (&buf)[CAP][NT], int& cnt,
+                                         float& tau, float tau0) {
+  for (int j = 0; __ballot(j < cnt) != 0ull; ++j) {                // wave-uniform trip count
+    const bool live = j < cnt;
+    const float cs = buf[j][threadIdx.x].s;
+    const int32_t ci = buf[j][threadIdx.x].i;
+    et_bubble<KK>(Ls, Li, cs, ci, live);
+  }
+  cnt = 0;
+  tau = fmaxf(Ls[KK - 1], tau0);
+}
+
+// Candidates of one tile -> the lane's buffer; the fill is looked at after every CE registers (`flush` may raise
+// tau).  `mine`: the tile's masked items (>> 4 h), `first`: the item of register 0 (item0 + 4 h).
+// Strict comparison is exact: a lane meets its items in ascending id order, so a later score EQUAL to the threshold
+// loses the tie anyway; it also keeps the -inf of the rows beyond the slice out.
+// With the reference's mask value (-FLT_MAX, below every real score; `lazy_mask`) the mask is applied lazily, inside
+// the candidate branch only: a masked item whose real score does not beat the threshold could not enter with
+// -FLT_MAX either (the threshold is -inf, and then every score is a candidate, or already >= -FLT_MAX).  Any other
+// mask value has rewritten the scores before (et_set_where).
+// `hinted` (wave-uniform): with thresholds from hint lists most tiles hold no candidate in the whole wave: the lane's
+// largest score against its threshold first (8 v_max3 + one compare instead of 16 compare-and-branch blocks).  With
+// the looser bounds of the prescan, or none, nearly every tile holds one, and the test would only add to it.
+template <int CE, int CAP, int NT, typename Flush>
+__device__ __forceinline__ void et_collect(const f32x16& acc, uint32_t mine, int first, bool lazy_mask,
+                                           float mask_value, bool hinted, const float& tau,
+                                           TopEntry (&buf)[CAP][NT], int& cnt, Flush&& flush) {
+  if (hinted) {
+    float mx = acc[0];
+#pragma unroll
+    for (int reg = 1; reg < 16; ++reg) mx = fmaxf(mx, acc[reg]);
+    if (__ballot(mx > tau) == 0ull) return;
+  }
+#pragma unroll
+  for (int part = 0; part < 16 / CE; ++part) {
+#pragma unroll
+    for (int q = 0; q < CE; ++q) {
+      const int reg = part * CE + q;
+      float sc = acc[reg];
+      if (sc > tau) {
+        if (lazy_mask && ((mine >> et_reg_item(reg)) & 1u)) sc = mask_value;
+        if (sc > tau) {
+          TopEntry c;
+          c.s = sc;
+          c.i = first + et_reg_item(reg);
+          buf[cnt][threadIdx.x] = c;
+          ++cnt;
+        }
+      }
+    }
+    if (__ballot(cnt > kEtFlushAt) != 0ull) flush();
+  }
+}
+
 template <int D, int KK, bool BIAS, bool SPLIT, bool PRESCAN>
 __global__ __launch_bounds__(kEtThreads) void mf_eval_topk_kernel(
     const float* __restrict__ U, const void* __restrict__ I_any, const float* __restrict__ item_bias,
@@ -423,16 +598,9 @@ __global__ __launch_bounds__(kEtThreads) void mf_eval_topk_kernel(
   uint4 us[3][KB];                                   // (unused, and removed by the compiler, in the f32 form)
   int64_t uid;
   const bool ok = et_row_user(users, row, nrows, num_users, err_flag, uid);
-  if constexpr (SPLIT) {
-    et_user_planes<D>(U, uid, ok, h, us);
-  } else {
-#pragma unroll
-    for (int q = 0; q < HALF / 4; ++q) {
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (ok) v = *reinterpret_cast<const float4*>(U + uid * D + h * HALF + 4 * q);
-      ub[4 * q + 0] = v.x; ub[4 * q + 1] = v.y; ub[4 * q + 2] = v.z; ub[4 * q + 3] = v.w;
-    }
-  }
+  const float* __restrict__ urow = U + (ok ? uid : 0) * D;   // (a bad id is not multiplied: nothing is loaded from it)
+  if constexpr (SPLIT) et_user_planes<KB>(urow, ok, h, us);
+  else et_user_half<HALF>(urow + h * HALF, ok, ub);
 
   // private list, threshold, buffer fill and mask cursor
   float Ls[KK];
@@ -444,27 +612,12 @@ __global__ __launch_bounds__(kEtThreads) void mf_eval_topk_kernel(
   for (int e = 0; e < (PRESCAN ? 16 : 1); ++e) gm[e] = -INFINITY;
   int cnt = 0;
   const bool lazy_mask = mask_value <= -3.0e38f;     // uniform
-  // the next TWO masked item ids stay in registers: the load that refills the second one is issued
-  // a tile (or more) before its value is needed, so the sweep never waits on it
-  int64_t m_cur = 0, m_end = 0;
-  int next_masked = 0x7fffffff, after_next = 0x7fffffff;
-  if (mask_ptr && row < nrows) {
-    m_cur = mask_ptr[row];
-    m_end = mask_ptr[row + 1];
-    while (m_cur < m_end && mask_idx[m_cur] < item_lo) ++m_cur;   // masks below this slice
-    if (m_cur < m_end) next_masked = (int)mask_idx[m_cur];
-    if (m_cur + 1 < m_end) after_next = (int)mask_idx[m_cur + 1];
-  }
-
+  EtMaskCursor masks(mask_ptr, mask_idx, row, nrows, item_lo);
+  [[maybe_unused]] long long ph_flush = 0;
   auto flush = [&]() {
-    for (int j = 0; __ballot(j < cnt) != 0ull; ++j) {              // wave-uniform trip count
-      const bool live = j < cnt;
-      const float cs = s_buf[j][threadIdx.x].s;
-      const int32_t ci = s_buf[j][threadIdx.x].i;
-      et_bubble<KK>(Ls, Li, cs, ci, live);
-    }
-    cnt = 0;
-    tau = fmaxf(Ls[KK - 1], tau0);
+    const long long t_f = ET_CLK();
+    et_flush(Ls, Li, s_buf, cnt, tau, tau0);
+    ph_flush += ET_CLK() - t_f;
   };
 
   // register staging of the item chunks: the loads of chunk c+1 are issued before the tiles of
@@ -492,183 +645,53 @@ __global__ __launch_bounds__(kEtThreads) void mf_eval_topk_kernel(
         *reinterpret_cast<uint4*>(dst + (q / ROW16) * ROWB + 16 * (q % ROW16)) = stage[v];
     }
   };
-#if YR_ET_PRIO == 3
-  switch ((blockIdx.x + 5 * blockIdx.y) % 3) {
-    case 0: __builtin_amdgcn_s_setprio(0); break;
-    case 1: __builtin_amdgcn_s_setprio(1); break;
-    default: __builtin_amdgcn_s_setprio(3); break;
-  }
-#endif
-  [[maybe_unused]] long long ph_mfma = 0, ph_mask = 0, ph_epi = 0, ph_flush = 0, ph_sync = 0, ph_total = ET_CLK();
+  [[maybe_unused]] long long ph_mfma = 0, ph_mask = 0, ph_epi = 0, ph_sync = 0, ph_total = ET_CLK();
   fetch(item_lo);
   stash(s_items[0], 0);
   __syncthreads();
   int cur = 0;
   for (int c0 = item_lo; c0 < item_hi; c0 += (int)step) {
     const bool more = c0 + step < item_hi;
-#ifndef YR_ET_EXP_NOSTAGE
     if (more) fetch(c0 + (int)step);                 // lands in the other buffer at the end of this chunk
-#endif
     const unsigned char* chunk = s_items[cur];
 
 #pragma unroll 1
     for (int t = 0; t < CH / 32; ++t) {
       const int item0 = c0 + t * 32;
       if (item0 >= item_hi) break;                   // wave-uniform
-      // ---- scores: acc[reg] = <item item0 + row(reg, h), user of this lane>
+      // ---- scores: acc[reg] = <item item0 + et_reg_item(reg) + 4 h, user of this lane>, started from the bias
       const long long t_a = ET_CLK();
-#if YR_ET_PRIO == 1
-      __builtin_amdgcn_s_setprio(3);
-#elif YR_ET_PRIO == 2
-      __builtin_amdgcn_s_setprio(0);
-#endif
-      f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (BIAS) {                                    // accumulator register 4 g + j holds item 8 g + 4 h + j of the tile
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float4 b4 = *reinterpret_cast<const float4*>(&s_bias[cur][t * 32 + 8 * g + 4 * h]);
-          acc[4 * g + 0] = b4.x; acc[4 * g + 1] = b4.y; acc[4 * g + 2] = b4.z; acc[4 * g + 3] = b4.w;
-        }
-      }
-      if constexpr (SPLIT) {
-        // item row i of the tile, dims 16 kb + 8 h + j: one ds_read_b128 per plane and block; the small terms first
-        const unsigned char* src = chunk + (t * 32 + i) * ROWB + 16 * h;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-          const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(src + 32 * kb);
-          const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(src + 2 * D + 32 * kb);
-          const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(src + 4 * D + 32 * kb);
-          const bf16x8 u1 = __builtin_bit_cast(bf16x8, us[0][kb]);
-          const bf16x8 u2 = __builtin_bit_cast(bf16x8, us[1][kb]);
-          const bf16x8 u3 = __builtin_bit_cast(bf16x8, us[2][kb]);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, u1, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u3, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, u2, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, u1, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u2, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u1, acc, 0, 0, 0);
-        }
-      } else {
-        const float* src = reinterpret_cast<const float*>(chunk) + (t * 32 + i) * (D + 4) + h * HALF;
-#pragma unroll
-        for (int q = 0; q < HALF / 4; ++q) {
-          const float4 b = *reinterpret_cast<const float4*>(src + 4 * q);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.x, ub[4 * q + 0], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.y, ub[4 * q + 1], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.z, ub[4 * q + 2], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b.w, ub[4 * q + 3], acc, 0, 0, 0);
-        }
-      }
+      f32x16 acc = zero16();
+      if (BIAS) et_start_acc(acc, &s_bias[cur][t * 32], h);
+      if constexpr (SPLIT) et_tile_split<KB>(acc, chunk + (t * 32 + i) * ROWB + 16 * h, us);
+      else et_tile_f32<HALF>(acc, reinterpret_cast<const float*>(chunk) + (t * 32 + i) * (D + 4) + h * HALF, ub);
 #ifdef YR_ET_STAMPS
       asm volatile("" ::"v"(acc[0]));                 // the scores have arrived
 #endif
-#if YR_ET_PRIO == 1
-      __builtin_amdgcn_s_setprio(0);
-#elif YR_ET_PRIO == 2
-      __builtin_amdgcn_s_setprio(3);
-#endif
       const long long t_b = ET_CLK();
       ph_mfma += t_b - t_a;
-      // ---- masked items of this tile (bit r = item item0 + r), shifted to this half's rows
-      uint32_t bits = 0;
-#ifdef YR_ET_EXP_NOMASK      // timing experiment only (wrong results): the mask lists are ignored
-      next_masked = 0x7fffffff;
-#endif
-      if constexpr (PRESCAN) {
-        // the sample skips most of the catalogue: jump over the entries below this tile eight at a time (the walk
-        // below is one dependent load per entry)
-        if (next_masked < item0) {
-          const int64_t before = m_cur;
-          while (m_cur + 8 < m_end && (int)mask_idx[m_cur + 8] < item0) m_cur += 8;
-          if (m_cur != before) {
-            next_masked = (int)mask_idx[m_cur];
-            after_next = m_cur + 1 < m_end ? (int)mask_idx[m_cur + 1] : 0x7fffffff;
-          }
-        }
-      }
-      while (next_masked < item0 + 32) {
-        if (next_masked >= item0) bits |= 1u << (next_masked - item0);
-        ++m_cur;
-        next_masked = after_next;
-        after_next = m_cur + 1 < m_end ? (int)mask_idx[m_cur + 1] : 0x7fffffff;
-      }
-      // With the reference's mask value (-FLT_MAX, below every real score) the mask is applied
-      // lazily, inside the candidate branch only: a masked item whose real score does not beat the
-      // threshold could not enter with -FLT_MAX either (the threshold is -inf, and then every
-      // score is a candidate, or already >= -FLT_MAX).  Any other mask value rewrites the scores first.
+      // ---- masked items of this tile, shifted to this half's rows
+      if constexpr (PRESCAN) masks.skip_to(item0);
+      const uint32_t bits = masks.walk<32>(item0);
       const long long t_c = ET_CLK();
       ph_mask += t_c - t_b;
       const uint32_t mine = bits >> (4 * h);
-      if ((PRESCAN || !lazy_mask) && __ballot(bits != 0) != 0ull) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg)
-          if ((mine >> ((reg & 3) + 8 * (reg >> 2))) & 1u) acc[reg] = mask_value;
-      }
-      if (item0 + 32 > item_hi) {                    // wave-uniform: last, partial tile of the slice
-        const uint32_t beyond = (~0u << (item_hi - item0)) >> (4 * h);
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg)
-          if ((beyond >> ((reg & 3) + 8 * (reg >> 2))) & 1u) acc[reg] = -INFINITY;   // not an item
-      }
+      if ((PRESCAN || !lazy_mask) && __ballot(bits != 0) != 0ull) et_set_where(acc, mine, mask_value);
+      if (item0 + 32 > item_hi)                      // wave-uniform: last, partial tile of the slice: not items
+        et_set_where(acc, (~0u << (item_hi - item0)) >> (4 * h), -INFINITY);
       if constexpr (PRESCAN) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) gm[reg] = fmaxf(gm[reg], acc[reg]);
-      }
-      // ---- candidates -> private buffer.  Strict comparison is exact: a lane meets its items in
-      // ascending id order, so a later score EQUAL to the threshold loses the tie anyway; it also
-      // keeps the -inf of the rows beyond the slice out.
-      // With thresholds from hint lists most tiles hold no candidate in the whole wave: the lane's largest score
-      // against its threshold first (8 v_max3 + one compare instead of 16 compare-and-branch blocks).  With the
-      // looser bounds of the prescan, or none, nearly every tile holds one, and the test would only add to it.
-      bool scan = !PRESCAN;
-#if YR_ET_EARLY_OUT
-      if (!PRESCAN && row_tau) {                     // wave-uniform
-        float mx = acc[0];
-#pragma unroll
-        for (int reg = 1; reg < 16; ++reg) mx = fmaxf(mx, acc[reg]);
-        scan = __ballot(mx > tau) != 0ull;
-      }
-#endif
-      if (scan)
-#pragma unroll
-      for (int half = 0; half < 16 / CE; ++half) {
-#pragma unroll
-        for (int q = 0; q < CE; ++q) {
-          const int reg = half * CE + q;
-          float sc = acc[reg];
-#ifdef YR_ET_EXP_NOSCAN      // timing experiment only (wrong results): nothing ever becomes a candidate
-          if (sc == 12345.678f) {
-#else
-          if (sc > tau) {
-#endif
-            if (lazy_mask && ((mine >> ((reg & 3) + 8 * (reg >> 2))) & 1u)) sc = mask_value;
-            if (sc > tau) {
-              TopEntry c;
-              c.s = sc;
-              c.i = item0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-              s_buf[cnt][threadIdx.x] = c;
-              ++cnt;
-            }
-          }
-        }
-        if (__ballot(cnt > kEtFlushAt) != 0ull) {
-          const long long t_f = ET_CLK();
-          flush();
-          ph_flush += ET_CLK() - t_f;
-        }
+      } else {
+        et_collect<CE>(acc, mine, item0 + 4 * h, lazy_mask, mask_value, row_tau != nullptr, tau, s_buf, cnt, flush);
       }
       ph_epi += ET_CLK() - t_c;
     }
     const long long t_s = ET_CLK();
     // one barrier per chunk: everyone is done reading s_items[cur ^ 1] since the previous barrier,
     // so the next chunk can be written there while slower waves still read s_items[cur]
-#ifdef YR_ET_EXP_NOSTAGE     // timing experiment only (wrong results): no global loads, no LDS writes, no barrier
-#elif defined(YR_ET_EXP_NOBARRIER)   // timing experiment only (wrong results): the waves of a workgroup never wait for each other
-    if (more) stash(s_items[cur ^ 1], cur ^ 1);
-#else
     if (more) stash(s_items[cur ^ 1], cur ^ 1);
     __syncthreads();
-#endif
     ph_sync += ET_CLK() - t_s;
     cur ^= 1;
   }
@@ -706,7 +729,8 @@ __global__ __launch_bounds__(kEtThreads) void mf_eval_topk_kernel(
 //   interval n (between barriers n and n + 1):  waves 0-3: scores(t) in 2t, rest(t) in 2t + 1;  waves 4-7: one later
 //   tile t lives in stage t & 1: written in intervals 2t - 3 (rows 0-15, waves 0-3) and 2t - 2 (rows 16-31, waves 4-7),
 //   read in 2t - 1 and 2t; the next tile of that stage (t + 2) is written from 2t + 1 on.
-// Same instruction order per tile as mf_eval_topk_kernel<.., SPLIT>: identical scores, identical lists.
+// The same products in the same order per tile as mf_eval_topk_kernel<.., SPLIT> (et_products6): identical scores,
+// identical lists.
 #ifdef YR_PP_TRACE
 // -DYR_PP_TRACE: shader-clock stamps of waves 0 and 4 of workgroup (1, 0) around every interval of tiles 100..163
 __device__ long long g_pp_trace[2][64][8];
@@ -719,9 +743,6 @@ __device__ long long g_pp_trace[2][64][8];
 constexpr int kPpWaves = 8;
 constexpr int kPpThreads = kPpWaves * kWave;             // 512
 constexpr int kPpUsers = kPpWaves * kEtUsersPerWave;     // 256 per workgroup
-#ifndef YR_PP_PRIO
-#define YR_PP_PRIO 0          // experiments: 1 = the scores interval at s_setprio 3, 2 = the rest interval
-#endif
 #ifndef YR_PP_TILES_D64
 #define YR_PP_TILES_D64 2     // tiles per interval at D = 64 with lists up to 10 entries (two: the matrix interval as
                               // long as at D = 128; with 16-entry lists the second accumulator spills)
@@ -770,33 +791,15 @@ __global__ __launch_bounds__(kPpThreads) void mf_eval_topk_pp_kernel(
   uint4 us[3][KB];                                      // B operand: the user's row, three planes
   int64_t uid;
   const bool ok = et_row_user(users, row, nrows, num_users, err_flag, uid);
-  et_user_planes<D>(U, uid, ok, h, us);
+  et_user_planes<KB>(U + (ok ? uid : 0) * D, ok, h, us);
   float Ls[KK];
   int32_t Li[KK];
   const float tau0 = et_start_lists<KK>(Ls, Li, k, ok, row, row_tau, gmax, parts);
   float tau = fmaxf(Ls[KK - 1], tau0);
   int cnt = 0;
   const bool lazy_mask = mask_value <= -3.0e38f;
-  int64_t m_cur = 0, m_end = 0;
-  int next_masked = 0x7fffffff, after_next = 0x7fffffff;
-  if (mask_ptr && row < nrows) {
-    m_cur = mask_ptr[row];
-    m_end = mask_ptr[row + 1];
-    while (m_cur < m_end && mask_idx[m_cur] < item_lo) ++m_cur;
-    if (m_cur < m_end) next_masked = (int)mask_idx[m_cur];
-    if (m_cur + 1 < m_end) after_next = (int)mask_idx[m_cur + 1];
-  }
-
-  auto flush = [&]() {
-    for (int j = 0; __ballot(j < cnt) != 0ull; ++j) {
-      const bool live = j < cnt;
-      const float cs = s_buf[j][threadIdx.x].s;
-      const int32_t ci = s_buf[j][threadIdx.x].i;
-      et_bubble<KK>(Ls, Li, cs, ci, live);
-    }
-    cnt = 0;
-    tau = fmaxf(Ls[KK - 1], tau0);
-  };
+  EtMaskCursor masks(mask_ptr, mask_idx, row, nrows, item_lo);
+  auto flush = [&]() { et_flush(Ls, Li, s_buf, cnt, tau, tau0); };
 
   // this role's 16 rows of a tile: global -> registers (one rest phase ahead), registers -> LDS.  No branches: rows
   // beyond the slice read its last row (rest() turns their scores into -inf), and at D = 64, where a role's 384
@@ -857,33 +860,21 @@ __global__ __launch_bounds__(kPpThreads) void mf_eval_topk_pp_kernel(
   };
   // the accumulators' start: the decoder bias; without bias the first product of a tile takes the constant 0 instead
   auto start_acc = [&](int tile) {
-    if constexpr (BIAS) {                              // accumulator register 4 g + q holds item 8 g + 4 h + q of its tile
+    if constexpr (BIAS) {
 #pragma unroll
-      for (int j = 0; j < TILES; ++j) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float4 b4 = *reinterpret_cast<const float4*>(&s_bias[tile % NBUF][32 * j + 8 * g + 4 * h]);
-          acc[j][4 * g + 0] = b4.x; acc[j][4 * g + 1] = b4.y; acc[j][4 * g + 2] = b4.z; acc[j][4 * g + 3] = b4.w;
-        }
-      }
+      for (int j = 0; j < TILES; ++j) et_start_acc(acc[j], &s_bias[tile % NBUF][32 * j], h);
     }
   };
-  auto products = [&](int set, int b0) {               // the small terms first, as in the four-wave kernel
+  auto products = [&](int set, int b0) {
 #pragma unroll
     for (int j = 0; j < SETB; ++j) {
       const int b = b0 + j;
       if (b < NB) {
-        const bf16x8 u1 = __builtin_bit_cast(bf16x8, us[0][b % KB]);
-        const bf16x8 u2 = __builtin_bit_cast(bf16x8, us[1][b % KB]);
-        const bf16x8 u3 = __builtin_bit_cast(bf16x8, us[2][b % KB]);
         f32x16& c = acc[b / KB];
-        const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[set][2][j], u1, (!BIAS && b % KB == 0) ? zero : c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[set][0][j], u3, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[set][1][j], u2, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[set][1][j], u1, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[set][0][j], u2, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[set][0][j], u1, c, 0, 0, 0);
+        const f32x16 zero = zero16();
+        et_products6(c, (!BIAS && b % KB == 0) ? zero : c, A[set][0][j], A[set][1][j], A[set][2][j],
+                     __builtin_bit_cast(bf16x8, us[0][b % KB]), __builtin_bit_cast(bf16x8, us[1][b % KB]),
+                     __builtin_bit_cast(bf16x8, us[2][b % KB]));
       }
     }
   };
@@ -909,23 +900,18 @@ __global__ __launch_bounds__(kPpThreads) void mf_eval_topk_pp_kernel(
   // mask, threshold test, candidates of step `tile` (the scores are in acc[0 .. TILES))
   auto rest = [&](int tile) {
     const int step0 = item_lo + MT * tile;
-    uint64_t bits = 0;
-#ifdef YR_PP_EXP_NOWALK
-    next_masked = 0x7fffffff;
-#endif
-    while (next_masked < step0 + MT) {
-      if (next_masked >= step0) bits |= 1ull << (next_masked - step0);
-      ++m_cur;
-      next_masked = after_next;
-      after_next = m_cur + 1 < m_end ? (int)mask_idx[m_cur + 1] : 0x7fffffff;
-    }
+    const auto bits = masks.walk<MT>(step0);           // bit r = item step0 + r: tile j's word is bits >> 32 j
+    // The two set loops below are this kernel's OWN copy of et_set_where, for a measured reason: with the shared piece
+    // the compiler tests each word for emptiness first and lays the whole rest phase out differently (500 of 4,600
+    // instruction lines at D = 64 with two tiles), and the sweep without hints ran 0.4-1.3 % slower than before the
+    // pieces were shared (D = 64, k = 10: 1.232 -> 1.244 ms; with this copy 1.216: profiles/eval_sweep_pieces_ab.txt).
     if (!lazy_mask && __ballot(bits != 0) != 0ull) {
 #pragma unroll
       for (int j = 0; j < TILES; ++j) {
         const uint32_t mine = (uint32_t)(bits >> (32 * j)) >> (4 * h);
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
-          if ((mine >> ((reg & 3) + 8 * (reg >> 2))) & 1u) acc[j][reg] = mask_value;
+          if ((mine >> et_reg_item(reg)) & 1u) acc[j][reg] = mask_value;
       }
     }
     if (step0 + MT > item_hi) {                        // wave-uniform: last, partial step of the slice
@@ -935,7 +921,7 @@ __global__ __launch_bounds__(kPpThreads) void mf_eval_topk_pp_kernel(
         const uint32_t beyond = (valid >= 32 ? 0u : ~0u << valid) >> (4 * h);
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
-          if ((beyond >> ((reg & 3) + 8 * (reg >> 2))) & 1u) acc[j][reg] = -INFINITY;
+          if ((beyond >> et_reg_item(reg)) & 1u) acc[j][reg] = -INFINITY;
       }
     }
     float mx = acc[0][0];
@@ -944,10 +930,6 @@ __global__ __launch_bounds__(kPpThreads) void mf_eval_topk_pp_kernel(
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) mx = fmaxf(mx, acc[j][reg]);
     }
-#ifdef YR_PP_EXP_NOSCAN
-    asm volatile("" ::"v"(mx));
-    return;
-#endif
     if (__ballot(mx > tau) == 0ull) return;            // no lane of the wave has a candidate in this step
     // The four waves of a role wait for each other every interval, so this must be short in the common case: which of
     // the scores pass (a bit each), then one candidate per lane and round, lowest register first (ascending item
@@ -966,7 +948,7 @@ __global__ __launch_bounds__(kPpThreads) void mf_eval_topk_pp_kernel(
           float sc = acc[j][0];
 #pragma unroll
           for (int q = 1; q < 16; ++q) sc = reg == q ? acc[j][q] : sc;
-          const int pos = (reg & 3) + 8 * (reg >> 2);
+          const int pos = et_reg_item(reg);
           if (lazy_mask && ((mine >> pos) & 1u)) sc = mask_value;
           if (sc > tau) {                              // (tau may have risen in a flush since `pass` was taken)
             TopEntry c;
@@ -991,19 +973,7 @@ __global__ __launch_bounds__(kPpThreads) void mf_eval_topk_pp_kernel(
 #pragma unroll 1
   for (int t = 0; t < T; ++t) {
     PP_STAMP(0);
-#if YR_PP_PRIO == 1
-    __builtin_amdgcn_s_setprio(3);
-#elif YR_PP_PRIO == 2
-    __builtin_amdgcn_s_setprio(0);
-#endif
-#ifndef YR_PP_EXP_NOMFMA     // (YR_PP_EXP_*: timing experiments only, wrong results)
     scores(t);
-#endif
-#if YR_PP_PRIO == 1
-    __builtin_amdgcn_s_setprio(0);
-#elif YR_PP_PRIO == 2
-    __builtin_amdgcn_s_setprio(3);
-#endif
     PP_STAMP(1);
     // the matrix instructions are register-only: without this the scheduler moves 23 of the 24 BELOW the barrier,
     // into the interval that belongs to the partner's
@@ -1011,27 +981,17 @@ __global__ __launch_bounds__(kPpThreads) void mf_eval_topk_pp_kernel(
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
     PP_STAMP(2);
-#ifndef YR_PP_EXP_NOSTAGE
     if (!STREAM && t + 2 < T) stash(t + 2);
-#endif
     PP_STAMP(5);
-#ifndef YR_PP_EXP_NOREST
     rest(t);
-#else
-    asm volatile("" ::"v"(acc[0][0]), "v"(acc[TILES - 1][15]));   // (the scores stay computed)
-#endif
     PP_STAMP(6);
-#ifndef YR_PP_EXP_NOOPERANDS
     if (t + 1 < T) {
       if (!STREAM) first_blocks(t + 1);
       start_acc(t + 1);
     }
-#endif
     PP_STAMP(7);
     // the global loads LAST: the mask walk waits with vmcnt(0) for its own (older) load and would wait for these too
-#ifndef YR_PP_EXP_NOSTAGE
     if (!STREAM && t + 3 < T) fetch(t + 3);
-#endif
     PP_STAMP(3);
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
@@ -1053,8 +1013,8 @@ __global__ __launch_bounds__(kPpThreads) void mf_eval_topk_pp_kernel(
 //     three bf16 terms in registers in the split form) — amortised over the TILES tiles;
 //   * the slab's matrix instructions go into each of the TILES accumulators, in the narrow kernels' order.
 // After the last slab lane (i, h) holds its own user's scores for 16 items of each tile, the shape the narrow forms'
-// selection consumes: the same mask cursor, candidate buffers, lockstep flush (et_bubble), early-out, list start
-// (hint thresholds), half-wave merge and slice merge.  Catalogue slices are cut by the same rule (et_slices).
+// selection consumes: the same mask cursor, candidate collector (et_collect: buffers, early-out), lockstep flush, list
+// start (hint thresholds), half-wave merge and slice merge.  Catalogue slices are cut by the same rule (et_slices).
 // One stage buffer (two barriers per slab): with two workgroups per CU the other workgroup's matrix instructions
 // cover the staging.  This form NEVER runs a prescan: YR_EVAL_FORCE_PRESCAN / YR_EVAL_NO_PRESCAN are accepted and
 // change nothing; YR_EVAL_TWO_ROLES / YR_EVAL_FOUR_WAVES likewise (one wide form).
@@ -1100,26 +1060,8 @@ __global__ __launch_bounds__(kEtThreads, 2) void mf_eval_topk_wide_kernel(
   float tau = fmaxf(Ls[KK - 1], tau0);
   int cnt = 0;
   const bool lazy_mask = mask_value <= -3.0e38f;     // uniform
-  int64_t m_cur = 0, m_end = 0;
-  int next_masked = 0x7fffffff, after_next = 0x7fffffff;
-  if (mask_ptr && row < nrows) {
-    m_cur = mask_ptr[row];
-    m_end = mask_ptr[row + 1];
-    while (m_cur < m_end && mask_idx[m_cur] < item_lo) ++m_cur;   // masks below this slice
-    if (m_cur < m_end) next_masked = (int)mask_idx[m_cur];
-    if (m_cur + 1 < m_end) after_next = (int)mask_idx[m_cur + 1];
-  }
-
-  auto flush = [&]() {
-    for (int j = 0; __ballot(j < cnt) != 0ull; ++j) {              // wave-uniform trip count
-      const bool live = j < cnt;
-      const float cs = s_buf[j][threadIdx.x].s;
-      const int32_t ci = s_buf[j][threadIdx.x].i;
-      et_bubble<KK>(Ls, Li, cs, ci, live);
-    }
-    cnt = 0;
-    tau = fmaxf(Ls[KK - 1], tau0);
-  };
+  EtMaskCursor masks(mask_ptr, mask_idx, row, nrows, item_lo);
+  auto flush = [&]() { et_flush(Ls, Li, s_buf, cnt, tau, tau0); };
 
   // slab `sl` of the MT item rows from c0 on: global -> LDS (zeros beyond the slice); the bias with slab 0
   auto stage = [&](int c0, int sl) {
@@ -1137,56 +1079,15 @@ __global__ __launch_bounds__(kEtThreads, 2) void mf_eval_topk_wide_kernel(
     }
   };
 
-  // mask, tail, threshold test and candidates of one tile: the epilogue of mf_eval_topk_kernel
+  // mask, tail, threshold test and candidates of one tile
   auto select = [&](f32x16& acc, int item0) {
-    uint32_t bits = 0;
-    while (next_masked < item0 + 32) {
-      if (next_masked >= item0) bits |= 1u << (next_masked - item0);
-      ++m_cur;
-      next_masked = after_next;
-      after_next = m_cur + 1 < m_end ? (int)mask_idx[m_cur + 1] : 0x7fffffff;
-    }
+    const uint32_t bits = masks.walk<32>(item0);
     const uint32_t mine = bits >> (4 * h);
-    if (!lazy_mask && __ballot(bits != 0) != 0ull) {
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg)
-        if ((mine >> ((reg & 3) + 8 * (reg >> 2))) & 1u) acc[reg] = mask_value;
-    }
-    if (item0 + 32 > item_hi) {                      // wave-uniform: last, partial tile of the slice
-      const uint32_t beyond = (~0u << (item_hi - item0)) >> (4 * h);
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg)
-        if ((beyond >> ((reg & 3) + 8 * (reg >> 2))) & 1u) acc[reg] = -INFINITY;   // not an item
-    }
-    bool scan = true;
-#if YR_ET_EARLY_OUT
-    if (row_tau) {                                   // wave-uniform
-      float mx = acc[0];
-#pragma unroll
-      for (int reg = 1; reg < 16; ++reg) mx = fmaxf(mx, acc[reg]);
-      scan = __ballot(mx > tau) != 0ull;
-    }
-#endif
-    if (scan)
-#pragma unroll
-    for (int part = 0; part < 16 / kEtCheckEvery; ++part) {
-#pragma unroll
-      for (int q = 0; q < kEtCheckEvery; ++q) {
-        const int reg = part * kEtCheckEvery + q;
-        float sc = acc[reg];
-        if (sc > tau) {
-          if (lazy_mask && ((mine >> ((reg & 3) + 8 * (reg >> 2))) & 1u)) sc = mask_value;
-          if (sc > tau) {
-            TopEntry c;
-            c.s = sc;
-            c.i = item0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            s_buf[cnt][threadIdx.x] = c;
-            ++cnt;
-          }
-        }
-      }
-      if (__ballot(cnt > kEtFlushAt) != 0ull) flush();
-    }
+    if (!lazy_mask && __ballot(bits != 0) != 0ull) et_set_where(acc, mine, mask_value);
+    if (item0 + 32 > item_hi)                        // wave-uniform: last, partial tile of the slice: not items
+      et_set_where(acc, (~0u << (item_hi - item0)) >> (4 * h), -INFINITY);
+    et_collect<kEtCheckEvery>(acc, mine, item0 + 4 * h, lazy_mask, mask_value, row_tau != nullptr, tau, s_buf, cnt,
+                              flush);
   };
 
 #pragma unroll 1
@@ -1199,68 +1100,21 @@ __global__ __launch_bounds__(kEtThreads, 2) void mf_eval_topk_wide_kernel(
       // B operand of this slab: f32 dims [sl SD + h SD/2, + SD/2); SPLIT dims sl SD + 16 kb + 8 h + j, three planes
       float ub[SPLIT ? 1 : HALF];
       uint4 us[3][KB];                               // (unused, and removed by the compiler, in the f32 form)
-      if constexpr (SPLIT) {
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-          float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-          if (ok) {
-            lo = *reinterpret_cast<const float4*>(urow + sl * SD + 16 * kb + 8 * h);
-            hi = *reinterpret_cast<const float4*>(urow + sl * SD + 16 * kb + 8 * h + 4);
-          }
-          et_split3x8(lo, hi, us[0][kb], us[1][kb], us[2][kb]);
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < HALF / 4; ++q) {
-          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (ok) v = *reinterpret_cast<const float4*>(urow + sl * SD + h * HALF + 4 * q);
-          ub[4 * q + 0] = v.x; ub[4 * q + 1] = v.y; ub[4 * q + 2] = v.z; ub[4 * q + 3] = v.w;
-        }
-      }
+      if constexpr (SPLIT) et_user_planes<KB>(urow + sl * SD, ok, h, us);
+      else et_user_half<HALF>(urow + sl * SD + h * HALF, ok, ub);
       __syncthreads();
       if (sl == 0) {
 #pragma unroll
         for (int t = 0; t < TILES; ++t) {
           acc[t] = zero16();
-          if (BIAS) {                                // accumulator register 4 g + j holds item 8 g + 4 h + j of the tile
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const float4 b4 = *reinterpret_cast<const float4*>(&s_bias[t * 32 + 8 * g + 4 * h]);
-              acc[t][4 * g + 0] = b4.x; acc[t][4 * g + 1] = b4.y; acc[t][4 * g + 2] = b4.z; acc[t][4 * g + 3] = b4.w;
-            }
-          }
+          if (BIAS) et_start_acc(acc[t], &s_bias[t * 32], h);
         }
       }
 #pragma unroll
       for (int t = 0; t < TILES; ++t) {
-        if constexpr (SPLIT) {
-          const unsigned char* src = s_items + (t * 32 + i) * ROWB + 16 * h;
-#pragma unroll
-          for (int kb = 0; kb < KB; ++kb) {
-            const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(src + 32 * kb);
-            const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(src + 2 * SD + 32 * kb);
-            const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(src + 4 * SD + 32 * kb);
-            const bf16x8 u1 = __builtin_bit_cast(bf16x8, us[0][kb]);
-            const bf16x8 u2 = __builtin_bit_cast(bf16x8, us[1][kb]);
-            const bf16x8 u3 = __builtin_bit_cast(bf16x8, us[2][kb]);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, u1, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u3, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, u2, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, u1, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u2, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, u1, acc[t], 0, 0, 0);
-          }
-        } else {
-          const float* src = reinterpret_cast<const float*>(s_items) + (t * 32 + i) * (SD + 4) + h * HALF;
-#pragma unroll
-          for (int q = 0; q < HALF / 4; ++q) {
-            const float4 b = *reinterpret_cast<const float4*>(src + 4 * q);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.x, ub[4 * q + 0], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.y, ub[4 * q + 1], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.z, ub[4 * q + 2], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(b.w, ub[4 * q + 3], acc[t], 0, 0, 0);
-          }
-        }
+        if constexpr (SPLIT) et_tile_split<KB>(acc[t], s_items + (t * 32 + i) * ROWB + 16 * h, us);
+        else
+          et_tile_f32<HALF>(acc[t], reinterpret_cast<const float*>(s_items) + (t * 32 + i) * (SD + 4) + h * HALF, ub);
       }
     }
 #pragma unroll
@@ -1404,44 +1258,63 @@ struct EtArgs {
   bool two_roles;       // the sweep as mf_eval_topk_pp_kernel (row blocks of 256)
 };
 
+// every sweep kernel's parameter list begins with the same fourteen values; `tail` is the rest of it
+template <typename... P, typename... Tail>
+void et_run(void (*kernel)(P...), dim3 grid, int threads, hipStream_t s, const EtArgs& a, Tail... tail) {
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, s, a.U, a.items, a.item_bias, a.users, a.nrows, a.num_users,
+                     a.num_items, a.mask_ptr, a.mask_idx, a.mask_value, a.k, a.out, a.partial, a.per, tail...);
+}
+
 template <int DD, int KK, bool BB, bool SS, bool PP>
 void et_launch_one(const EtArgs& a, dim3 grid, int chunk_stride, hipStream_t s) {
-  hipLaunchKernelGGL((mf_eval_topk_kernel<DD, KK, BB, SS, PP>), grid, dim3(kEtThreads), 0, s, a.U, a.items, a.item_bias,
-                     a.users, a.nrows, a.num_users, a.num_items, a.mask_ptr, a.mask_idx, a.mask_value, a.k, a.out,
-                     a.partial, a.per, a.gmax, a.parts, chunk_stride, a.row_tau, a.err_flag);
+  et_run(mf_eval_topk_kernel<DD, KK, BB, SS, PP>, grid, kEtThreads, s, a, a.gmax, a.parts, chunk_stride, a.row_tau,
+         a.err_flag);
+}
+template <int DD, int KK, bool BB>
+void et_launch_pp(const EtArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)((a.nrows + kPpUsers - 1) / kPpUsers), a.slices);
+  et_run(mf_eval_topk_pp_kernel<DD, KK, BB, (DD == 64 && KK <= 10) ? YR_PP_TILES_D64 : 1>, grid, kPpThreads, s, a,
+         (const float*)a.gmax, a.parts, a.row_tau, a.err_flag);
+}
+template <int DD, int KK, bool BB, bool SS>
+void et_launch_wide(const EtArgs& a, hipStream_t s) {
+  et_run(mf_eval_topk_wide_kernel<DD, KK, BB, SS>, dim3(a.row_blocks, a.slices), kEtThreads, s, a, a.row_tau,
+         a.err_flag);
 }
 
+// the list length: the smallest of 4 / 10 / 16 / 32 entries that holds k, where the form has it
 template <int DD, bool BB, bool SS>
 void et_launch(const EtArgs& a, hipStream_t s) {
-  if (a.gmax) {
-    // every stride-th stage of the catalogue, dealt to `parts` workgroups
-    constexpr int CHP = et_chunk_items(DD, 4, SS);
-    const int chunks = (a.num_items + CHP - 1) / CHP;
-    const int sample = std::min(kEtSampleItems, std::max(CHP, a.num_items / 8));
-    const int stride = std::max(1, chunks / std::max(1, sample / CHP));
-    et_launch_one<DD, 4, BB, SS, true>(a, dim3(a.row_blocks, (unsigned)a.parts), stride, s);
-  }
-  if constexpr (SS && (DD == 64 || DD == 128)) {
-    if (a.two_roles) {
-      const dim3 grid2((unsigned)((a.nrows + kPpUsers - 1) / kPpUsers), a.slices);
-#define YR_ET_PP(KK)                                                                                                  \
-  hipLaunchKernelGGL((mf_eval_topk_pp_kernel<DD, KK, BB, (DD == 64 && KK <= 10) ? YR_PP_TILES_D64 : 1>), grid2, dim3(kPpThreads), 0, s, a.U, a.items, a.item_bias, \
-                     a.users, a.nrows, a.num_users, a.num_items, a.mask_ptr, a.mask_idx, a.mask_value, a.k, a.out,     \
-                     a.partial, a.per, a.gmax, a.parts, a.row_tau, a.err_flag)
-      if (a.k <= 4) YR_ET_PP(4);
-      else if (a.k <= 10) YR_ET_PP(10);
-      else if constexpr (DD == 64) YR_ET_PP(16);       // (D = 128 with 16-entry lists spills: not offered, see et_pp_wanted)
-#undef YR_ET_PP
-      return;
+  if constexpr (DD > 128) {
+    if (a.k <= 4) et_launch_wide<DD, 4, BB, SS>(a, s);
+    else if (a.k <= 10) et_launch_wide<DD, 10, BB, SS>(a, s);
+    else et_launch_wide<DD, 16, BB, SS>(a, s);        // (k > 16: refused by the caller)
+  } else {
+    if (a.gmax) {
+      // every stride-th stage of the catalogue, dealt to `parts` workgroups
+      constexpr int CHP = et_chunk_items(DD, 4, SS);
+      const int chunks = (a.num_items + CHP - 1) / CHP;
+      const int sample = std::min(kEtSampleItems, std::max(CHP, a.num_items / 8));
+      const int stride = std::max(1, chunks / std::max(1, sample / CHP));
+      et_launch_one<DD, 4, BB, SS, true>(a, dim3(a.row_blocks, (unsigned)a.parts), stride, s);
     }
+    if constexpr (SS && (DD == 64 || DD == 128)) {
+      if (a.two_roles) {
+        if (a.k <= 4) et_launch_pp<DD, 4, BB>(a, s);
+        else if (a.k <= 10) et_launch_pp<DD, 10, BB>(a, s);
+        else if constexpr (DD == 64) et_launch_pp<DD, 16, BB>(a, s);   // (D = 128 with 16-entry lists spills: not offered, see et_pp_wanted)
+        return;
+      }
+    }
+    const dim3 grid(a.row_blocks, a.slices);
+    if (a.k <= 4) et_launch_one<DD, 4, BB, SS, false>(a, grid, 0, s);
+    else if (a.k <= 10) et_launch_one<DD, 10, BB, SS, false>(a, grid, 0, s);
+    else if (a.k <= 16) et_launch_one<DD, 16, BB, SS, false>(a, grid, 0, s);
+    else if constexpr (DD <= 64) et_launch_one<DD, 32, BB, SS, false>(a, grid, 0, s);   // (D = 128: refused by the caller)
   }
-  const dim3 grid(a.row_blocks, a.slices);
-  if (a.k <= 4) et_launch_one<DD, 4, BB, SS, false>(a, grid, 0, s);
-  else if (a.k <= 10) et_launch_one<DD, 10, BB, SS, false>(a, grid, 0, s);
-  else if (a.k <= 16) et_launch_one<DD, 16, BB, SS, false>(a, grid, 0, s);
-  else if constexpr (DD <= 64) et_launch_one<DD, 32, BB, SS, false>(a, grid, 0, s);   // (D = 128: refused by the caller)
 }
 
+// bias x split -> template arguments, for the narrow and the wide widths
 template <int DD>
 void et_launch_d(const EtArgs& a, bool split, hipStream_t s) {
   if (a.item_bias) {
@@ -1450,30 +1323,6 @@ void et_launch_d(const EtArgs& a, bool split, hipStream_t s) {
   } else {
     if (split) et_launch<DD, false, true>(a, s);
     else et_launch<DD, false, false>(a, s);
-  }
-}
-
-template <int DD, bool BB, bool SS>
-void et_launch_wide(const EtArgs& a, hipStream_t s) {
-  const dim3 grid(a.row_blocks, a.slices);
-#define YR_ET_WIDE(KK)                                                                                              \
-  hipLaunchKernelGGL((mf_eval_topk_wide_kernel<DD, KK, BB, SS>), grid, dim3(kEtThreads), 0, s, a.U, a.items,         \
-                     a.item_bias, a.users, a.nrows, a.num_users, a.num_items, a.mask_ptr, a.mask_idx, a.mask_value,  \
-                     a.k, a.out, a.partial, a.per, a.row_tau, a.err_flag)
-  if (a.k <= 4) YR_ET_WIDE(4);
-  else if (a.k <= 10) YR_ET_WIDE(10);
-  else YR_ET_WIDE(16);                                 // (k > 16: refused by the caller)
-#undef YR_ET_WIDE
-}
-
-template <int DD>
-void et_launch_wide_d(const EtArgs& a, bool split, hipStream_t s) {
-  if (a.item_bias) {
-    if (split) et_launch_wide<DD, true, true>(a, s);
-    else et_launch_wide<DD, true, false>(a, s);
-  } else {
-    if (split) et_launch_wide<DD, false, true>(a, s);
-    else et_launch_wide<DD, false, false>(a, s);
   }
 }
 }  // namespace
@@ -1560,9 +1409,9 @@ extern "C" int yr_mf_eval_topk_bias(const float* U, const float* I, const float*
     case 32: et_launch_d<32>(a, split, s); break;
     case 64: et_launch_d<64>(a, split, s); break;
     case 128: et_launch_d<128>(a, split, s); break;
-    case 256: et_launch_wide_d<256>(a, split, s); break;
-    case 512: et_launch_wide_d<512>(a, split, s); break;
-    default: et_launch_wide_d<1024>(a, split, s); break;
+    case 256: et_launch_d<256>(a, split, s); break;
+    case 512: et_launch_d<512>(a, split, s); break;
+    default: et_launch_d<1024>(a, split, s); break;
   }
   if (S > 1)
     hipLaunchKernelGGL(mf_eval_merge_kernel, dim3((unsigned)((nrows + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
