@@ -421,7 +421,8 @@ int yr_cdae_hidden_bwd(float *dz, const float *z, int act, const int64_t *user, 
  *   1e-12) * act'(y), then dz[b,:] += g W_o[i,:] (dz zero on entry), dW_o[i,:] += g z[b,:], db_o[i] += g
  *   (float atomics; both buffers zero on entry), count (spread,
  *   YR_COUNT_WORDS, zero on entry) += positions.  Nothing carries the 1 / count of the mean: the consumers apply
- *   it (yr_cdae_hidden_bwd scale_dz = 1, yr_adam_dense_flat scaled[k] = 1).  H a multiple of 4, <= 256. */
+ *   it (yr_cdae_hidden_bwd scale_dz = 1, yr_adam_dense_flat scaled[k] = 1).  H a multiple of 4, <= 256 (a
+ *   half-wave per position), or 512 / 1,024 (a wave per position); any other H > 256: YR_ERR_UNSUPPORTED. */
 int yr_cdae_compact_pair(const float *x, const float *negative_mask, int64_t B, int64_t I, uint64_t seed,
                          double p, int32_t *cols, float *vals, int32_t *count, int32_t *loss_cols,
                          float *loss_targets, int32_t *loss_count, void *stream);
@@ -635,10 +636,13 @@ int yr_adam_dense(float *p, float *g, float *m, float *v, int64_t n,
 #define YR_ADAM_MULTI_MAX 16
 /* yr_adam_dense_flat: up to YR_ADAM_MULTI_MAX tensors of ANY size in one launch at 16 bytes per lane
  * (every buffer 16-byte aligned).  touched[k] (HOST array of device pointers,
- * entries may be NULL): one byte per row of row_width[k] floats (row_width / 4 a power of two <= 64) — the
+ * entries may be NULL): one byte per row of row_width[k] floats (row_width / 4 a power of two <= 64, or
+ * row_width 512 / 1,024: such a launch orders a row's mark by a workgroup barrier instead of inside a wave) — the
  * gradient of a row is read, cleared and unmarked only where the mark is set (every row is still updated, with
  * grad = 0 elsewhere).  clear[k] = 1: the gradient is cleared after it is read; 2: only where it is non-zero.  scaled[k] != 0 (with
- * grad_count, a spread count, see YR_COUNT_SLOTS): the gradient is multiplied by 1 / count first. */
+ * grad_count, a spread count, see YR_COUNT_SLOTS): the gradient is multiplied by 1 / count first.
+ * Order of the checks: count and the arrays, then every tensor's own arguments (YR_ERR_BADARG), then the mode
+ * (YR_ERR_UNSUPPORTED) — a refused row width is reported before an unknown mode. */
 int yr_adam_dense_flat(float *const *p, float *const *g, float *const *m, float *const *v,
                        const int64_t *n, uint8_t *const *touched, const int *row_width, const int *clear,
                        const int *scaled, const int32_t *grad_count, int count, double lr, double step_size, double bc2_sqrt, double beta1,
@@ -704,7 +708,8 @@ int yr_cdae_sparse_dwh_t(const int32_t *cols, const float *vals, const int32_t *
 /* yr_cdae_hidden_bwd_dwh_t = yr_cdae_hidden_bwd + yr_cdae_sparse_dwh_t in one launch (a workgroup per batch row keeps
  * the row's dz in registers): db_h += dz (float atomics: db_h zero on entry), dV[user] += dz (user marked), dWhT rows
  * of the input items += dz * val (items marked), loss of the step from the decoder's partials (workgroup 0).
- * pos_count: the spread count of loss positions (always needed for the loss; divides dz when scale_dz != 0).  H <= 512. */
+ * pos_count: the spread count of loss positions (always needed for the loss; divides dz when scale_dz != 0).
+ * H <= 1,024: a thread keeps up to two hidden units (H <= 512) or four. */
 int yr_cdae_hidden_bwd_dwh_t(const int32_t *cols, const float *vals, const int32_t *count, const float *dz,
                              const float *z, int act, int scale_dz, const int32_t *pos_count,
                              const int64_t *user, int64_t B, int64_t I, int H, int64_t num_users, float *dV,

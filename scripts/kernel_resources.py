@@ -47,6 +47,14 @@ BUDGETS = [
     (r"void yr::mf_scores_mfma_wide_kernel<(256|512|1024)>", 256, 72 * 1024, "score GEMM in slabs: as the sweep"),
     (r"void yr::et_hint_bound_kernel<(256|512|1024)>", 64, 0, "the dot product is a loop: eight waves per SIMD"),
     (r"void yr::adam_dual_wide_kernel<(true|false)>", 64, 1024, "streaming pass, as adam_dual_kernel"),
+    # the wide hidden sizes (512 / 1024) of CDAE on list batches
+    (r"void yr::cdae_sampled_decode_wide_kernel<(512|1024), (true|false)>", 128, 34 * 1024,
+     "a wave per position, two W_o rows of 8 / 16 registers in flight beside z and dz: four waves per SIMD "
+     "(512 / 4 -> 128) = four workgroups per CU, 4 x 33 KB of 160 KB LDS (staged list 16 KB + 4 x H floats of dz)"),
+    (r"void yr::cdae_hidden_bwd_dwh_t_kernel<(2|4)>", 64, 17 * 1024,
+     "up to four hidden units per thread in registers: eight waves per SIMD (512 / 8 -> 64), the staged list in LDS"),
+    (r"void yr::adam_flat_kernel<(true|false), true>", 64, 1024,
+     "streaming pass with a barrier per chunk for marked rows of 512 / 1,024 floats: eight waves per SIMD, as the plain form"),
 ]
 # Scratch (spilled registers) per lane.  The forms the benchmark and the trainers run by default — width 64, summation
 # order free — must have none; the deterministic-order forms and some forms of the other widths are held at 64 VGPRs by

@@ -37,18 +37,26 @@ import torch
 from . import engine, optim
 
 
+WIDE_HIDDEN = (512, 1024)      # hidden sizes above 256 with the sampled decoder, row marks and the transposed W_h
+
+
 class CDAEStep:
-    def __init__(self, model, optimizer, negative_sampling=True, decoder="auto", transposed_wh=False):
+    def __init__(self, model, optimizer, negative_sampling=True, decoder="auto", transposed_wh=False, row_marks=True):
         """``decoder``: "sampled" — forward, loss and the three decoder gradients on the loss positions only
         (NS-BCE reads nothing else; needs a negative mask), "dense" — the full-catalogue products on the matrix
-        cores, "auto" — sampled when the loss is NS-BCE and the hidden size allows it.
+        cores, "auto" — sampled when the loss is NS-BCE and the hidden size allows it (a multiple of 4 whose quarter is
+        a power of two up to 256, or 512 / 1,024).
         ``transposed_wh``: between ``acquire()`` (implicit in the first step) and ``release()`` the step trains a
         TRANSPOSED working copy of W_h and of its two Adam moments ([I, H]): an input item is then a 512-byte row
         for the encoder and for dW_h (contiguous float atomics straight into the gradient, no scratch, one launch),
         and the Adam launch reads / clears the gradient rows of the batch's items only.  Adam is element-wise, so
         the layout changes nothing in the arithmetic; ``release()`` writes the three tensors back — the caller must
         do that before anything else reads ``hidden_layer.weight`` or the optimizer state (CDAETrainer.train does,
-        at the end of the epoch)."""
+        at the end of the epoch).
+        ``row_marks``: False keeps the step off row marks at any width — every Adam launch then reads and clears all of
+        dW_h and dV, and there is no transposed working copy (what every hidden size without marks runs, e.g. 320;
+        scripts/bench_cdae_wide.py times the widths 512 / 1,024 that way for comparison).  With the default, marks hold
+        wherever the width allows them, for the dense decoder too."""
         from . import optim
         if not isinstance(optimizer, optim.Adam):
             raise NotImplementedError("CDAEStep: optimizer adam or adamw")
@@ -59,9 +67,9 @@ class CDAEStep:
         if H % 4:
             raise NotImplementedError("CDAEStep: hidden size must be a multiple of 4")
         # row marks (gradient rows read / cleared only where the batch touched them) need H / 4 lanes per row to
-        # tile a wave
-        self.row_marks = (H // 4) & (H // 4 - 1) == 0 and H // 4 <= 64
-        can_sample = self.negative_sampling and self.row_marks and H <= 256
+        # tile a wave, or — rows of 512 and 1,024 floats — to tile a workgroup (yr_adam_dense_flat's barrier form)
+        self.row_marks = bool(row_marks) and (((H // 4) & (H // 4 - 1) == 0 and H // 4 <= 64) or H in WIDE_HIDDEN)
+        can_sample = self.negative_sampling and self.row_marks and (H <= 256 or H in WIDE_HIDDEN)
         if decoder == "auto":
             decoder = "sampled" if can_sample else "dense"
         if decoder not in ("sampled", "dense") or (decoder == "sampled" and not can_sample):
@@ -204,7 +212,7 @@ class CDAEStep:
             engine.gemm_f32(self.G, self.z, transA=True, out=self.dWo, alpha_count=self.count, rowsum=self.dbo)
             engine.gemm_f32(self.G, Wo, out=self.dz, accumulate=True, split_k=max(1, min(256, Wo.shape[0] // 256)),
                             alpha_count=self.count)
-        if wt is not None and self.hidden_size <= 512:
+        if wt is not None and self.hidden_size <= 1024:
             # hidden layer's backward, db_h, dV, dW_h^T and the step's loss in one launch (db_h accumulates: the
             # Adam launch clears it)
             engine.cdae_hidden_bwd_dwh_t(rows, self.dz, self.z, model._hidden_act, user_id, self.count, self.dV,

@@ -255,6 +255,7 @@ __global__ __launch_bounds__(kBlock) void cdae_sparse_dwh_t_kernel(
 // yr_cdae_hidden_bwd + yr_cdae_sparse_dwh_t: one launch and one round trip through dz less (10 + 5 -> 6 us).
 constexpr int kHbRows = 1;      // batch rows per workgroup (4, with their db_h contributions summed before the atomic,
                                 // was slower: 12.6 against 10.3 us — the rows' list passes then run one after the other)
+template <int UPT>               // hidden units per thread: 2 (H <= 512), 4 (H <= 1,024)
 __global__ __launch_bounds__(kBlock) void cdae_hidden_bwd_dwh_t_kernel(
     const int32_t* __restrict__ cols, const float* __restrict__ vals, const int32_t* __restrict__ count, int64_t cpp,
     const float* __restrict__ dz, const float* __restrict__ z, int act, int scale_dz,
@@ -269,29 +270,35 @@ __global__ __launch_bounds__(kBlock) void cdae_hidden_bwd_dwh_t_kernel(
   const int lane = threadIdx.x & (kWave - 1);
   const int32_t npos = spread_count(pos_count, lane);             // every lane of every wave takes part
   const float alpha = scale_dz ? (npos > 0 ? 1.0f / (float)npos : 0.0f) : 1.0f;
-  // H <= kBlock in practice; a thread keeps the gradient of its hidden units (up to 2 per thread: H <= 512)
-  const int h0 = threadIdx.x, h1 = threadIdx.x + kBlock;
+  // H <= kBlock in practice; a thread keeps the gradient of its hidden units threadIdx.x + kBlock e, e < UPT
   const int64_t r_lo = (int64_t)blockIdx.x * kHbRows;
-  float g0[kHbRows], g1[kHbRows];
+  float g[kHbRows][UPT];
   int64_t us[kHbRows];
-  float b0 = 0.0f, b1 = 0.0f;
+  float b[UPT];
+#pragma unroll
+  for (int e = 0; e < UPT; ++e) b[e] = 0.0f;
 #pragma unroll
   for (int q = 0; q < kHbRows; ++q) {                             // all loads of the workgroup's rows first
     const int64_t r = min(r_lo + q, B - 1);
     const bool live = r_lo + q < B;
     us[q] = user[r];
-    g0[q] = (live && h0 < H) ? dz[r * H + h0] : 0.0f;
-    g1[q] = (live && h1 < H) ? dz[r * H + h1] : 0.0f;
-    const float y0 = (live && h0 < H) ? z[r * H + h0] : 0.0f;
-    const float y1 = (live && h1 < H) ? z[r * H + h1] : 0.0f;
-    g0[q] *= alpha;
-    g1[q] *= alpha;
-    if (act == 1) { g0[q] *= y0 * (1.0f - y0); g1[q] *= y1 * (1.0f - y1); }
-    b0 += g0[q];
-    b1 += g1[q];
+    float y[UPT];
+#pragma unroll
+    for (int e = 0; e < UPT; ++e) g[q][e] = (live && threadIdx.x + kBlock * e < H) ? dz[r * H + threadIdx.x + kBlock * e] : 0.0f;
+#pragma unroll
+    for (int e = 0; e < UPT; ++e) y[e] = (live && threadIdx.x + kBlock * e < H) ? z[r * H + threadIdx.x + kBlock * e] : 0.0f;
+#pragma unroll
+    for (int e = 0; e < UPT; ++e) g[q][e] *= alpha;
+    if (act == 1) {
+#pragma unroll
+      for (int e = 0; e < UPT; ++e) g[q][e] *= y[e] * (1.0f - y[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < UPT; ++e) b[e] += g[q][e];
   }
-  if (h0 < H) atomicAdd(dbh + h0, b0);
-  if (h1 < H) atomicAdd(dbh + h1, b1);
+#pragma unroll
+  for (int e = 0; e < UPT; ++e)
+    if (threadIdx.x + kBlock * e < H) atomicAdd(dbh + threadIdx.x + kBlock * e, b[e]);
 #pragma unroll 1
   for (int q = 0; q < kHbRows; ++q) {
     const int64_t r = r_lo + q;
@@ -299,15 +306,18 @@ __global__ __launch_bounds__(kBlock) void cdae_hidden_bwd_dwh_t_kernel(
     const int64_t u = us[q];
     const bool ok = (uint64_t)u < (uint64_t)num_users;
     if (ok && threadIdx.x == 0 && touched_users) touched_users[u] = 1;
-    if (ok && h0 < H) atomicAdd(dV + u * H + h0, g0[q]);
-    if (ok && h1 < H) atomicAdd(dV + u * H + h1, g1[q]);
+#pragma unroll
+    for (int e = 0; e < UPT; ++e)
+      if (ok && threadIdx.x + kBlock * e < H) atomicAdd(dV + u * H + threadIdx.x + kBlock * e, g[q][e]);
     for (int skip = 0;; skip += kListCap) {
       const int n = gather_row_list(cols, vals, count, cpp, r, skip, s_pre, s_col, s_val);
       for (int j = threadIdx.x; j < n; j += kBlock) touched_items[s_col[j]] = 1;
-      if (h0 < H)
-        for (int j = 0; j < n; ++j) atomicAdd(dWhT + (int64_t)s_col[j] * H + h0, g0[q] * s_val[j]);
-      if (h1 < H)
-        for (int j = 0; j < n; ++j) atomicAdd(dWhT + (int64_t)s_col[j] * H + h1, g1[q] * s_val[j]);
+#pragma unroll
+      for (int e = 0; e < UPT; ++e) {
+        const int h = threadIdx.x + kBlock * e;
+        if (h < H)
+          for (int j = 0; j < n; ++j) atomicAdd(dWhT + (int64_t)s_col[j] * H + h, g[q][e] * s_val[j]);
+      }
       const bool more = skip + n < s_pre[kListParts];
       __syncthreads();
       if (!more) break;
@@ -344,7 +354,8 @@ __global__ __launch_bounds__(kBlock) void cdae_hidden_bwd_dwh_t_kernel(
 //     dW_o[i, :] += g z[b, :]          float atomics, 512 contiguous bytes per position
 //     db_o[i]    += g
 //   count (spread, see YR_COUNT_SLOTS) += positions.  dW_o / db_o must be zero where no earlier position of
-//   this step wrote; dz zero on entry when S > 1.
+//   this step wrote; dz zero on entry when S > 1.  H <= 256; H = 512 and 1,024 take the wave-per-position form
+//   further down (cdae_sampled_decode_wide_kernel).
 constexpr int kHalf = 32;
 constexpr int kHalves = kBlock / kHalf;
 
@@ -498,6 +509,168 @@ __global__ __launch_bounds__(kBlock) void cdae_sampled_decode_kernel(
     int tot = 0;
 #pragma unroll
     for (int k = 0; k < kHalves; ++k) { tl += s_loss[k]; tot += s_done[k]; }
+    partial_loss[r * splits + split] = tl;
+    spread_count_add(count, blockIdx.y * gridDim.x + blockIdx.x, tot);
+  }
+}
+
+// The wide form (H = 512 and 1,024): a whole WAVE per position.  In the half-wave layout a lane would hold 4 x 32 row
+// registers at H = 1,024 (z, dz, two W_o rows in flight) and s_dz would take 32 KB.  Here lane l holds floats
+// l + 64 k, k < HW / 64 (RowGeom<HW> of csrc/bpr_mf.hip): every load and every float atomic of a wave covers 256
+// contiguous bytes, the dot product is one 64-lane DPP sum, s_dz is 4 x HW floats.  Everything else is the narrow
+// form: the list staged in passes of kListCap, the splits of a row interleaved over the staged entries, two positions
+// per wave in flight, the waves combined in fixed order, dz stored at splits == 1 and added otherwise.
+// LOSS_ONLY: lane l holds floats [4 l + 256 k, 4 l + 256 k + 4) (16-byte loads, 1 KB per wave instruction), and a
+// position's BCE term is computed once, by the lane whose number is the position's place in its group of 64.
+__device__ __forceinline__ float wave_sum_dpp(float x) {
+  x = group_sum_dpp<32>(x);
+  return x + __shfl_xor(x, 32, kWave);
+}
+
+template <int HW, bool LOSS_ONLY>
+__global__ __launch_bounds__(kBlock) void cdae_sampled_decode_wide_kernel(
+    const int32_t* __restrict__ lcols, const float* __restrict__ lvals, const int32_t* __restrict__ lcount,
+    int64_t cpp, const float* __restrict__ z, const float* __restrict__ Wo, const float* __restrict__ bo, int act,
+    int splits, float* __restrict__ dz, float* __restrict__ dWo, float* __restrict__ dbo,
+    float* __restrict__ partial_loss, int32_t* __restrict__ count) {
+  static_assert(HW == 512 || HW == 1024, "wide hidden sizes");
+  constexpr int EPL = RowGeom<HW>::EPL;              // floats of a row per lane: 8 or 16
+  constexpr int kW = kWavesPerBlock;
+  __shared__ int s_pre[kListParts + 1];
+  __shared__ int32_t s_col[kListCap];
+  __shared__ float s_val[kListCap];
+  __shared__ float s_dz[LOSS_ONLY ? 1 : kW][LOSS_ONLY ? 1 : HW];
+  __shared__ float s_loss[kW];
+  __shared__ int s_done[kW];
+  const int64_t r = blockIdx.x;
+  const int split = blockIdx.y;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  float loss = 0.0f;
+  int done = 0;
+  if constexpr (LOSS_ONLY) {
+    float4 zr[EPL / 4];
+#pragma unroll
+    for (int k = 0; k < EPL / 4; ++k) zr[k] = ld4(z + r * HW + 4 * lane + 4 * kWave * k);
+    for (int skip = 0;; skip += kListCap) {
+      const int n = gather_row_list(lcols, lvals, lcount, cpp, r, skip, s_pre, s_col, s_val);
+      float pre_mine = 0.0f, t_mine = 0.0f;
+      bool have = false;
+      int slot = 0;
+      auto settle = [&]() {                           // every lane: the BCE term of the position it was handed
+        if (have) {
+          float y = pre_mine;
+          if (act == 1) y = 1.0f / (1.0f + expf(-y));
+          loss -= t_mine * fmaxf(logf(y), -100.0f) + (1.0f - t_mine) * fmaxf(logf(1.0f - y), -100.0f);
+        }
+        have = false;
+        slot = 0;
+      };
+      for (int j0 = split + wave * splits; j0 < n; j0 += 2 * kW * splits) {
+        const int j1 = j0 + kW * splits;
+        const bool two = j1 < n;
+        const int col0 = s_col[j0], col1 = s_col[two ? j1 : j0];
+        float4 w0[EPL / 4], w1[EPL / 4];
+#pragma unroll
+        for (int k = 0; k < EPL / 4; ++k) {
+          w0[k] = ld4(Wo + (int64_t)col0 * HW + 4 * lane + 4 * kWave * k);
+          w1[k] = ld4(Wo + (int64_t)col1 * HW + 4 * lane + 4 * kWave * k);
+        }
+        const float b0 = bo ? bo[col0] : 0.0f, b1 = bo ? bo[col1] : 0.0f;
+#pragma unroll
+        for (int which = 0; which < 2; ++which) {
+          if (which == 1 && !two) break;
+          float d = 0.0f;
+#pragma unroll
+          for (int k = 0; k < EPL / 4; ++k) {
+            const float4 w = which ? w1[k] : w0[k];
+            d += w.x * zr[k].x + w.y * zr[k].y + w.z * zr[k].z + w.w * zr[k].w;
+          }
+          d = wave_sum_dpp(d);
+          if (lane == slot) {
+            pre_mine = d + (which ? b1 : b0);
+            t_mine = s_val[which ? j1 : j0];
+            have = true;
+          }
+          ++done;
+          if (++slot == kWave) settle();
+        }
+      }
+      settle();
+      const bool more = skip + n < s_pre[kListParts];
+      __syncthreads();
+      if (!more) break;
+    }
+    loss = wave_sum_dpp(loss);                        // the lanes' own positions, fixed order
+  } else {
+    float zr[EPL], acc[EPL];
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+      zr[k] = z[r * HW + lane + kWave * k];
+      acc[k] = 0.0f;
+    }
+    for (int skip = 0;; skip += kListCap) {
+      const int n = gather_row_list(lcols, lvals, lcount, cpp, r, skip, s_pre, s_col, s_val);
+      // this workgroup's share of the staged entries: j = split, split + splits, ...; wave `wave` takes every kW-th of
+      // those, two at a time (the second W_o row is in flight while the first is used)
+      for (int j0 = split + wave * splits; j0 < n; j0 += 2 * kW * splits) {
+        const int j1 = j0 + kW * splits;
+        const bool two = j1 < n;
+        const int col0 = s_col[j0], col1 = s_col[two ? j1 : j0];
+        float w0[EPL], w1[EPL];
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) {
+          w0[k] = Wo[(int64_t)col0 * HW + lane + kWave * k];
+          w1[k] = Wo[(int64_t)col1 * HW + lane + kWave * k];
+        }
+        const float b0 = bo ? bo[col0] : 0.0f, b1 = bo ? bo[col1] : 0.0f;
+#pragma unroll
+        for (int which = 0; which < 2; ++which) {
+          if (which == 1 && !two) break;
+          const int col = which ? col1 : col0;
+          const float t = s_val[which ? j1 : j0];
+          float d = 0.0f;
+#pragma unroll
+          for (int k = 0; k < EPL; ++k) d += (which ? w1[k] : w0[k]) * zr[k];
+          d = wave_sum_dpp(d);
+          float y = d + (which ? b1 : b0);
+          if (act == 1) y = 1.0f / (1.0f + expf(-y));
+          loss -= t * fmaxf(logf(y), -100.0f) + (1.0f - t) * fmaxf(logf(1.0f - y), -100.0f);
+          float g = (y - t) / fmaxf((1.0f - y) * y, 1e-12f);
+          if (act == 1) g *= y * (1.0f - y);
+          ++done;
+          float* grow = dWo + (int64_t)col * HW + lane;
+#pragma unroll
+          for (int k = 0; k < EPL; ++k) {
+            acc[k] += g * (which ? w1[k] : w0[k]);
+            atomicAdd(grow + kWave * k, g * zr[k]);
+          }
+          if (lane == 0) atomicAdd(dbo + col, g);
+        }
+      }
+      const bool more = skip + n < s_pre[kListParts];
+      __syncthreads();
+      if (!more) break;
+    }
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) s_dz[wave][lane + kWave * k] = acc[k];
+  }
+  // combine the waves in fixed order
+  if (lane == 0) { s_loss[wave] = loss; s_done[wave] = done; }
+  __syncthreads();
+  if constexpr (!LOSS_ONLY) {
+    for (int h = threadIdx.x; h < HW; h += kBlock) {
+      float tsum = 0.0f;
+#pragma unroll
+      for (int k = 0; k < kW; ++k) tsum += s_dz[k][h];
+      if (splits > 1) atomicAdd(dz + r * HW + h, tsum);
+      else dz[r * HW + h] = tsum;
+    }
+  }
+  if (threadIdx.x == 0) {
+    float tl = 0.0f;
+    int tot = 0;
+#pragma unroll
+    for (int k = 0; k < kW; ++k) { tl += s_loss[k]; tot += s_done[k]; }
     partial_loss[r * splits + split] = tl;
     spread_count_add(count, blockIdx.y * gridDim.x + blockIdx.x, tot);
   }
@@ -667,7 +840,7 @@ extern "C" int yr_cdae_sampled_decode(const int32_t* loss_cols, const float* los
                                       int act, float* dz, float* dWo, float* dbo, float* partial_loss,
                                       int32_t* count, void* stream) {
   if (B < 0 || I <= 0 || H <= 0 || (act != 0 && act != 1)) return YR_ERR_BADARG;
-  if (H > 256) return YR_ERR_UNSUPPORTED;
+  if (H > 256 && H != 512 && H != 1024) return YR_ERR_UNSUPPORTED;   // before any pointer check
   if (B == 0) return 0;
   if (!loss_cols || !loss_targets || !loss_count || !z || !Wo || !partial_loss || !count) return YR_ERR_BADARG;
   if ((dz || dWo || dbo) && !(dz && dWo && dbo)) return YR_ERR_BADARG;      // all three gradients or none
@@ -680,8 +853,14 @@ extern "C" int yr_cdae_sampled_decode(const int32_t* loss_cols, const float* los
 #define YR_SD(NK, LO)                                                                                                 \
   hipLaunchKernelGGL((cdae_sampled_decode_kernel<NK, LO>), grid, dim3(kBlock), 0, s, loss_cols, loss_targets, loss_count, \
                      cpp, z, Wo, bo, H, act, splits, dz, dWo, dbo, partial_loss, count)
+#define YR_SDW(HW, LO)                                                                                                \
+  hipLaunchKernelGGL((cdae_sampled_decode_wide_kernel<HW, LO>), grid, dim3(kBlock), 0, s, loss_cols, loss_targets,    \
+                     loss_count, cpp, z, Wo, bo, act, splits, dz, dWo, dbo, partial_loss, count)
   if (H <= 128) { if (loss_only) YR_SD(4, true); else YR_SD(4, false); }
-  else { if (loss_only) YR_SD(8, true); else YR_SD(8, false); }
+  else if (H <= 256) { if (loss_only) YR_SD(8, true); else YR_SD(8, false); }
+  else if (H == 512) { if (loss_only) YR_SDW(512, true); else YR_SDW(512, false); }
+  else { if (loss_only) YR_SDW(1024, true); else YR_SDW(1024, false); }
+#undef YR_SDW
 #undef YR_SD
   return launch_status();
 }
@@ -700,15 +879,18 @@ extern "C" int yr_cdae_hidden_bwd_dwh_t(const int32_t* cols, const float* vals, 
                                         uint8_t* touched_users, float* dbh, float* dWhT, uint8_t* touched_items,
                                         const float* partial_loss, int64_t n_partials, float* stats,
                                         double* loss_accum, void* stream) {
-  if (B < 0 || I <= 0 || H <= 0 || H > 2 * kBlock || num_users <= 0 || n_partials < 0 || (act != 0 && act != 1))
+  if (B < 0 || I <= 0 || H <= 0 || H > 4 * kBlock || num_users <= 0 || n_partials < 0 || (act != 0 && act != 1))
     return YR_ERR_BADARG;
   if (B == 0) return 0;
   if (!cols || !vals || !count || !dz || !z || !pos_count || !user || !dV || !dbh || !dWhT || !touched_items)
     return YR_ERR_BADARG;
   if (n_partials > 0 && (!partial_loss || !stats)) return YR_ERR_BADARG;
-  hipLaunchKernelGGL(cdae_hidden_bwd_dwh_t_kernel, dim3((unsigned)((B + kHbRows - 1) / kHbRows)), dim3(kBlock), 0,
-                     (hipStream_t)stream, cols, vals, count, yr_cdae_sparse_part_columns(I), dz, z, act,
-                     scale_dz ? 1 : 0, pos_count, user, B, num_users, H,
-                     dV, touched_users, dbh, dWhT, touched_items, partial_loss, n_partials, stats, loss_accum);
+#define YR_HB(UPT)                                                                                                    \
+  hipLaunchKernelGGL(cdae_hidden_bwd_dwh_t_kernel<UPT>, dim3((unsigned)((B + kHbRows - 1) / kHbRows)), dim3(kBlock), 0, \
+                     (hipStream_t)stream, cols, vals, count, yr_cdae_sparse_part_columns(I), dz, z, act,              \
+                     scale_dz ? 1 : 0, pos_count, user, B, num_users, H, dV, touched_users, dbh, dWhT, touched_items, \
+                     partial_loss, n_partials, stats, loss_accum)
+  if (H <= 2 * kBlock) YR_HB(2); else YR_HB(4);
+#undef YR_HB
   return launch_status();
 }

@@ -178,7 +178,13 @@ struct AdamFlat {
   int count;
 };
 
-template <bool DECOUPLED>
+// WIDE: some tensor has marked rows of 512 or 1,024 floats (128 or 256 float4: more than a wave).  A chunk is kBlock
+// float4 from the start of its tensor and such a row is aligned to its own size, so the row lies inside ONE chunk; the
+// rule of adam_dual_wide_kernel then orders its mark: every lane of the chunk reads its row's mark, the workgroup
+// meets at a barrier, and only then does the row's first lane clear the mark.  The chunk loop is workgroup-uniform and
+// the barrier comes before the per-thread exits (lanes past the tensor's end, the tail lane), so all 256 threads reach
+// it in every chunk.  A separate instantiation: launches without wide marks run the code they always ran.
+template <bool DECOUPLED, bool WIDE>
 __global__ __launch_bounds__(kBlock) void adam_flat_kernel(AdamFlat t, AdamScalars c) {
   const int64_t chunks = t.chunk_end[t.count - 1];
   float inv_count = 1.0f;
@@ -191,6 +197,13 @@ __global__ __launch_bounds__(kBlock) void adam_flat_kernel(AdamFlat t, AdamScala
     for (int q = 0; q + 1 < t.count; ++q)
       if (ch >= t.chunk_end[q]) k = q + 1;
     const int64_t j = (ch - (k > 0 ? t.chunk_end[k - 1] : 0)) * kBlock + threadIdx.x;
+    bool marked = true;
+    if constexpr (WIDE) {
+      if (t.touched[k]) {                               // wave-uniform (k is)
+        marked = j < t.n4[k] && t.touched[k][j >> t.row4[k]] != 0;
+        __syncthreads();                                // every lane of every row of this chunk has read its mark
+      }
+    }
     if (j >= t.n4[k]) {
       if (j == t.n4[k] && t.tail[k]) {                // the 1-3 elements after the last whole float4
         float* p = reinterpret_cast<float*>(t.p[k] + j);
@@ -211,7 +224,7 @@ __global__ __launch_bounds__(kBlock) void adam_flat_kernel(AdamFlat t, AdamScala
     float4 P = t.p[k][j], M = t.m[k][j], V = t.v[k][j];
     float4 G = make_float4(0.f, 0.f, 0.f, 0.f);
     const int64_t row = j >> shift;
-    const bool has = tp ? tp[row] != 0 : true;
+    const bool has = WIDE ? marked : (tp ? tp[row] != 0 : true);
     if (has) {
       G = gp[j];
       const int clr = t.clear[k];
@@ -356,10 +369,10 @@ extern "C" int yr_adam_dense_flat(float* const* p, float* const* g, float* const
   if (count < 0 || count > YR_ADAM_MULTI_MAX) return YR_ERR_BADARG;
   if (count == 0) return 0;
   if (!p || !g || !m || !v || !n) return YR_ERR_BADARG;
-  if (mode != YR_OPT_ADAM && mode != YR_OPT_ADAMW) return YR_ERR_UNSUPPORTED;
   AdamFlat t{};
   int64_t chunks = 0;
   int used = 0;
+  bool wide = false;
   for (int k = 0; k < count; ++k) {
     if (n[k] < 0) return YR_ERR_BADARG;
     if (n[k] == 0) continue;
@@ -367,8 +380,12 @@ extern "C" int yr_adam_dense_flat(float* const* p, float* const* g, float* const
     if (!aligned16(p[k]) || !aligned16(g[k]) || !aligned16(m[k]) || !aligned16(v[k])) return YR_ERR_BADARG;
     uint8_t* tp = touched ? touched[k] : nullptr;
     const int rw = row_width ? row_width[k] : 0;
-    // the lanes of a marked row must sit in one wave (they all read the mark before one of them clears it)
-    if (tp && (rw <= 0 || (rw & 3) || n[k] % rw || rw / 4 > kWave || kWave % (rw / 4))) return YR_ERR_BADARG;
+    // the lanes of a marked row must sit in one wave (they all read the mark before one of them clears it) or, rows
+    // of 512 and 1,024 floats, in one chunk, ordered by a barrier (adam_flat_kernel<., true>)
+    const bool wide_row = tp && (rw == 512 || rw == 1024);
+    if (tp && (rw <= 0 || (rw & 3) || n[k] % rw || (!wide_row && (rw / 4 > kWave || kWave % (rw / 4)))))
+      return YR_ERR_BADARG;
+    wide = wide || wide_row;
     t.p[used] = (float4*)p[k]; t.g[used] = (float4*)g[k]; t.m[used] = (float4*)m[k]; t.v[used] = (float4*)v[k];
     t.touched[used] = tp;
     int lg = 0;
@@ -382,14 +399,18 @@ extern "C" int yr_adam_dense_flat(float* const* p, float* const* g, float* const
     t.chunk_end[used] = chunks;
     ++used;
   }
+  if (mode != YR_OPT_ADAM && mode != YR_OPT_ADAMW) return YR_ERR_UNSUPPORTED;   // after the tensors' own checks
   if (used == 0) return 0;
   t.count = used;
   t.grad_count = grad_count;
   const AdamScalars c = adam_scalars(lr, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay);
   const int grid = (int)(chunks < kMaxGrid ? chunks : kMaxGrid);
   hipStream_t s = (hipStream_t)stream;
-  if (mode == YR_OPT_ADAMW) hipLaunchKernelGGL((adam_flat_kernel<true>), dim3(grid), dim3(kBlock), 0, s, t, c);
-  else hipLaunchKernelGGL((adam_flat_kernel<false>), dim3(grid), dim3(kBlock), 0, s, t, c);
+  if (wide) {
+    if (mode == YR_OPT_ADAMW) hipLaunchKernelGGL((adam_flat_kernel<true, true>), dim3(grid), dim3(kBlock), 0, s, t, c);
+    else hipLaunchKernelGGL((adam_flat_kernel<false, true>), dim3(grid), dim3(kBlock), 0, s, t, c);
+  } else if (mode == YR_OPT_ADAMW) hipLaunchKernelGGL((adam_flat_kernel<true, false>), dim3(grid), dim3(kBlock), 0, s, t, c);
+  else hipLaunchKernelGGL((adam_flat_kernel<false, false>), dim3(grid), dim3(kBlock), 0, s, t, c);
   return launch_status();
 }
 
