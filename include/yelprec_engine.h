@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YR_ENGINE_VERSION 30
+#define YR_ENGINE_VERSION 31
 
 #define YR_ERR_UNSUPPORTED (-1) /* embedding width / option not compiled in   */
 #define YR_ERR_BADARG      (-2) /* null pointer, negative size, misalignment  */
@@ -777,6 +777,40 @@ int yr_dcn_score(const float *Au, int64_t ldau, const float *Bi, int64_t ldbi, c
                  const int64_t *users, int64_t n_eval, int64_t num_users, int64_t num_items, int H1, int H2,
                  const float *W2, const float *b2, const float *Wo, const float *bo, const float *cw, const float *cb,
                  int L, int F, float *scores, int64_t row_stride, int32_t *err_flag, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * S3Rec scoring               (reference models/s3rec.py:53-115,184-214 in eval() mode; trainers/s3rec_trainer.py
+ *   validate / evaluate call it through finetune / evaluate)
+ * The self-attention encoder, forward only, one workgroup per sequence (csrc/s3rec.hip):
+ *   h = item_emb[X] + pos_enc (the positional row at padded positions too; X <= 0 is padding, item_emb[0] an
+ *   ordinary row), then `blocks` times, with pad[j] = (X[j] <= 0):
+ *     per head: Q = h Wq^T, K = (h Wk^T) * pad[j] (the rows of the REAL positions are zeroed, s3rec.py:202),
+ *       V = h Wv^T, P = softmax over the keys j <= i of Q K^T / sqrt(E) (full-width heads), A_h = P V;
+ *     attn = concat_h(A_h) Wo^T + bo;  x1 = LayerNorm1(h + attn);  f = W2 relu(W1 x1 + b1) + b2;
+ *     h = LayerNorm2(h + f)   (s3rec.py:70 adds the block's input, not x1; biased variance, eps 1e-5).
+ * params: ONE packed f32 buffer (16-byte aligned), block after block, each block
+ *   Wq [heads][E][E] | Wk [heads][E][E] | Wv [heads][E][E] | Wo [E][heads * E] | bo [E] | ln1.weight [E] |
+ *   ln1.bias [E] | W1 [E][E] | b1 [E] | W2 [E][E] | b2 [E] | ln2.weight [E] | ln2.bias [E]
+ *   = (4 heads + 2) E^2 + 7 E floats (every Linear weight as PyTorch stores it: [out][in]).
+ * item_emb [num_items + 1][E], pos_enc [L][E], X int64 [B][L].  E in {16, 32, 64, 128}, 1 <= L <= 64,
+ * 1 <= heads <= 4, 1 <= blocks <= 4 (YR_ERR_UNSUPPORTED beyond).  An id outside [0, num_items] raises
+ * YR_FLAG_BAD_ITEM and reads nothing (a zero embedding row in the encoder, a zero score).
+ * yr_s3rec_encode: out [B][L][E] = h of every position (replaces _embedding_layer + _self_attention_block,
+ *   s3rec.py:96-97), or with last_only != 0 out [B][E] = h[:, L - 1] (s3rec.py:109-111: X[:, -1]).
+ * yr_s3rec_seq_scores: pos_preds[r] = <item_emb[pos_items[r]], h[r]> and the same for neg_items, r < rows = B L
+ *   (_sequence_prediction_layer, s3rec.py:98-99; padded positions included: the loss is a mean over B L).
+ * yr_s3rec_candidate_scores: pos_pred[b] = <item_emb[pos_item[b]], h_last[b]>, neg_preds[b, c] =
+ *   <item_emb[neg_items[b, c]], h_last[b]> for c < C (_prediction_layer per candidate, s3rec.py:111-114).
+ * ------------------------------------------------------------------------- */
+int yr_s3rec_encode(const float *item_emb, const float *pos_enc, const float *params, const int64_t *X, int64_t B,
+                    int L, int E, int heads, int blocks, int64_t num_items, int last_only, float *out,
+                    int32_t *err_flag, void *stream);
+int yr_s3rec_seq_scores(const float *item_emb, const float *h, const int64_t *pos_items, const int64_t *neg_items,
+                        int64_t rows, int E, int64_t num_items, float *pos_preds, float *neg_preds,
+                        int32_t *err_flag, void *stream);
+int yr_s3rec_candidate_scores(const float *item_emb, const float *h_last, const int64_t *pos_item,
+                              const int64_t *neg_items, int64_t B, int64_t C, int E, int64_t num_items,
+                              float *pos_pred, float *neg_preds, int32_t *err_flag, void *stream);
 
 #ifdef __cplusplus
 }

@@ -55,6 +55,11 @@ BUDGETS = [
      "up to four hidden units per thread in registers: eight waves per SIMD (512 / 8 -> 64), the staged list in LDS"),
     (r"void yr::adam_flat_kernel<(true|false), true>", 64, 1024,
      "streaming pass with a barrier per chunk for marked rows of 512 / 1,024 floats: eight waves per SIMD, as the plain form"),
+    # S3Rec scoring: the LDS tiles are dynamic (13 KB at E = 16, L <= 32 up to 146 KB at E = 128, L > 32), none static
+    (r"void yr::s3rec_encode_kernel<(16|32|64|128)>", 256, 1024,
+     "a workgroup per sequence, LDS-bound: one to two workgroups of four waves per CU at the reference's shapes "
+     "(81.5 KB at E = 64, L = 50), so two waves per SIMD (512 / 2 -> 256) is all the registers have to allow"),
+    (r"yr::s3rec_scores_kernel", 64, 0, "16 lanes per dot product, streaming: eight waves per SIMD"),
 ]
 # Scratch (spilled registers) per lane.  The forms the benchmark and the trainers run by default — width 64, summation
 # order free — must have none; the deterministic-order forms and some forms of the other widths are held at 64 VGPRs by

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # YR_ENGINE_LIB: measurement hook — an instrumented build of the same sources (scratch/inst_build.sh writes it to
 # a temp directory so that the product objects and library are never overwritten); unset in every product run.
 LIB_PATH = os.environ.get("YR_ENGINE_LIB") or os.path.join(_HERE, "libyelprec_engine.so")
-ENGINE_VERSION = 30
+ENGINE_VERSION = 31
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -118,6 +118,9 @@ SIGNATURES = {
                     _p, _p, _p, _p, _p, _p],
     "yr_dcn_score": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _p, _p, _p, _p, _p, _int, _int,
                      _p, _i64, _p, _p],
+    "yr_s3rec_encode": [_p, _p, _p, _p, _i64, _int, _int, _int, _int, _i64, _int, _p, _p, _p],
+    "yr_s3rec_seq_scores": [_p, _p, _p, _p, _i64, _int, _i64, _p, _p, _p, _p],
+    "yr_s3rec_candidate_scores": [_p, _p, _p, _p, _i64, _i64, _int, _i64, _p, _p, _p, _p],
 }
 
 # return types: an int status (0, a negative YR_ERR_* or a HIP error) unless listed here — checked against the header by

@@ -1226,3 +1226,78 @@ def dcn_score(Au, Bi, Pu, Pi, users, W2, b2, Wo, bo, cw, cb, out, err_flag=None)
                            out.stride(0) if n > 1 else num_items, _opt(err_flag, torch.int32, "flag"), _stream()),
           "yr_dcn_score")
     return out
+
+
+# ---- S3Rec scoring (csrc/s3rec.hip) ----
+S3REC_MAX_L, S3REC_MAX_HEADS, S3REC_MAX_BLOCKS = 64, 4, 4
+
+
+def s3rec_block_floats(E, heads):
+    """Floats of one block in the packed parameter buffer (layout: include/yelprec_engine.h)."""
+    return (4 * heads + 2) * E * E + 7 * E
+
+
+def s3rec_encode(item_emb, pos_enc, params, X, heads, blocks, last_only=False, out=None, err_flag=None):
+    """h [B, L, E] of every position of the sequences X [B, L] (int64), or h[:, L - 1] as [B, E] with ``last_only``
+    (yr_s3rec_encode): the embedding layer and the self-attention blocks in one launch."""
+    lib = _lib.load()
+    f32 = torch.float32
+    if X.dim() != 2 or item_emb.dim() != 2 or pos_enc.shape != (X.shape[1], item_emb.shape[1]):
+        raise EngineError(f"s3rec_encode: X [B, L], item_emb [num_items + 1, E], pos_enc [L, E] expected, got "
+                          f"{tuple(X.shape)} / {tuple(item_emb.shape)} / {tuple(pos_enc.shape)}")
+    (B, L), E = X.shape, item_emb.shape[1]
+    if params.numel() != blocks * s3rec_block_floats(E, heads):
+        raise EngineError(f"s3rec_encode: packed parameters hold {params.numel()} floats, "
+                          f"{blocks * s3rec_block_floats(E, heads)} expected")
+    shape = (B, E) if last_only else (B, L, E)
+    if out is None:
+        out = torch.empty(shape, dtype=f32, device=X.device)
+    elif tuple(out.shape) != shape:
+        raise EngineError(f"s3rec_encode: out {tuple(out.shape)}, expected {shape}")
+    check(lib.yr_s3rec_encode(_dev(item_emb, f32, "item_emb"), _dev(pos_enc, f32, "pos_enc"),
+                              _dev(params, f32, "params"), _dev(X, torch.int64, "X"), B, L, E, heads, blocks,
+                              item_emb.shape[0] - 1, 1 if last_only else 0, _dev(out, f32, "out"),
+                              _opt(err_flag, torch.int32, "flag"), _stream()), "yr_s3rec_encode")
+    return out
+
+
+def _s3rec_out(out, shapes, device, what):
+    if out is None:
+        return tuple(torch.empty(s, dtype=torch.float32, device=device) for s in shapes)
+    if len(out) != 2 or any(tuple(t.shape) != s for t, s in zip(out, shapes)):
+        raise EngineError(f"{what}: out must be two tensors of shapes {shapes}")
+    return tuple(out)
+
+
+def s3rec_seq_scores(item_emb, h, pos_items, neg_items, out=None, err_flag=None):
+    """(pos_preds, neg_preds), each [B * L]: <item_emb[items[b, i]], h[b, i]> at every position (yr_s3rec_seq_scores)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    E = item_emb.shape[1]
+    rows = h.numel() // E
+    if pos_items.numel() != rows or neg_items.numel() != rows:
+        raise EngineError("s3rec_seq_scores: one positive and one negative item per position expected")
+    pos, neg = _s3rec_out(out, ((rows,), (rows,)), h.device, "s3rec_seq_scores")
+    check(lib.yr_s3rec_seq_scores(_dev(item_emb, f32, "item_emb"), _dev(h, f32, "h"),
+                                  _dev(pos_items, torch.int64, "pos_items"), _dev(neg_items, torch.int64, "neg_items"),
+                                  rows, E, item_emb.shape[0] - 1, _dev(pos, f32, "pos_preds"), _dev(neg, f32, "neg_preds"),
+                                  _opt(err_flag, torch.int32, "flag"), _stream()), "yr_s3rec_seq_scores")
+    return pos, neg
+
+
+def s3rec_candidate_scores(item_emb, h_last, pos_item, neg_items, out=None, err_flag=None):
+    """(pos_pred [B, 1], neg_preds [B, C]): the last position's h against the positive and the C sampled candidates
+    (yr_s3rec_candidate_scores)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    B, E = h_last.shape
+    if neg_items.dim() != 2 or neg_items.shape[0] != B or neg_items.shape[1] < 1 or pos_item.numel() != B:
+        raise EngineError("s3rec_candidate_scores: pos_item [B] and neg_items [B, C >= 1] expected")
+    C = neg_items.shape[1]
+    pos, neg = _s3rec_out(out, ((B, 1), (B, C)), h_last.device, "s3rec_candidate_scores")
+    check(lib.yr_s3rec_candidate_scores(_dev(item_emb, f32, "item_emb"), _dev(h_last, f32, "h_last"),
+                                        _dev(pos_item, torch.int64, "pos_item"),
+                                        _dev(neg_items, torch.int64, "neg_items"), B, C, E, item_emb.shape[0] - 1,
+                                        _dev(pos, f32, "pos_pred"), _dev(neg, f32, "neg_preds"),
+                                        _opt(err_flag, torch.int32, "flag"), _stream()), "yr_s3rec_candidate_scores")
+    return pos, neg
