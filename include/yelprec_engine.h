@@ -167,7 +167,11 @@ int yr_adam_dense_dual(float *p0, float *g0, float *m0, float *v0, int64_t n0,
  *          the contributions of a row are summed in triplet order (the owner pass re-ranks every row by
  *          triplet id after its LDS sort), chunks are cut at tile boundaries, and a tile segment larger
  *          than a chunk (a few rows taking most of a batch; tables of a few hundred rows) is taken in windows
- *          of triplet ids; costs a few percent;
+ *          of triplet ids; costs a few percent.  Which item buckets are shared between workgroups (an
+ *          oversize bucket is summed in parts, a different order than whole) is a function of the batch alone, in
+ *          both modes: the sizing workgroups count the helper tasks and scratch slots the batch WANTS, and a
+ *          batch that wants more than the pools hold (512 tasks, 1,024 slots: several hundred oversize buckets
+ *          at once) has NO bucket shared — every bucket is summed whole by its owner;
  *   workspace: >= yr_bpr_mf_pull_workspace_bytes(B, num_users, num_items, D) bytes, 16-byte
  *          aligned, contents irrelevant on entry (a size computed for max_batch serves every
  *          B <= max_batch).

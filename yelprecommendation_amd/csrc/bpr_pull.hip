@@ -333,8 +333,9 @@ __device__ __forceinline__ void build_splits(const OwnerArgs& a, int builder) {
   if (parts > 1) {
     slot = atomicAdd(split_counters(a.split) + 1, parts);
     const int first = atomicAdd(split_counters(a.split), parts - 1);
-    // no room left (more than kMaxSlots / kMaxTasks parts in one batch): the bucket stays whole and the task
-    // entries it took are marked void
+    // no room left (more than kMaxSlots / kMaxTasks parts in one batch): the task entries it took are marked void.
+    // The counters go on counting what the batch wants: the item pass reads them, and past either pool it treats
+    // EVERY bucket as whole, whatever this workgroup found room for (see pools_hold there)
     const bool fits = slot + parts <= kMaxSlots && first + parts - 1 <= kMaxTasks;
     for (int q = 1; q < parts; ++q)
       if (first + q - 1 < kMaxTasks) split_tasks(a.split, a.b_nb)[first + q - 1] = make_int4(fits ? k : -1, q, 0, 0);
@@ -572,8 +573,14 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
        helper ? ks == (int)blockIdx.x : ks < a.bucket_end; ks += owners) {
     // workgroups start in slot order: the caller may put heavy buckets first (wave-uniform: kept in a scalar register)
     int k, part = 0, parts = 1;
+    // Which buckets are shared is a function of the batch alone: the sizing workgroups count every task and slot the
+    // batch WANTS (their sums do not depend on arrival order); a batch that wants more than the pools hold shares no
+    // bucket at all — every bucket is summed whole, the helpers leave at once.  (Which buckets had found room
+    // depended on the order of two global atomics; a whole and a shared bucket add in different orders.)
+    const bool pools_hold = USER || !a.split || (split_counters(a.split)[0] <= kMaxTasks &&
+                                                 split_counters(a.split)[1] <= kMaxSlots);   // two scalar loads
     if (helper) {
-      if (ks >= min(split_counters(a.split)[0], kMaxTasks)) break;
+      if (!pools_hold || ks >= split_counters(a.split)[0]) break;
       const int4 task = split_tasks(a.split, a.nb)[ks];
       k = __builtin_amdgcn_readfirstlane(task.x);
       part = __builtin_amdgcn_readfirstlane(task.y);
@@ -581,7 +588,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
     } else {
       k = __builtin_amdgcn_readfirstlane(a.order ? a.order[ks] : ks);
     }
-    if (!USER && a.split) parts = __builtin_amdgcn_readfirstlane(split_parts(a.split)[k]);
+    if (!USER && a.split && pools_hold) parts = __builtin_amdgcn_readfirstlane(split_parts(a.split)[k]);
     // this workgroup's share of the bucket: the tiles [t_begin, t_end)
     // (an integer division runs on the vector unit: the results are moved back to scalar registers, or they would
     // cost the item pass two VGPRs it does not have — 12 B of scratch per lane, caught by scripts/kernel_resources.py)
