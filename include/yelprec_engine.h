@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YR_ENGINE_VERSION 31
+#define YR_ENGINE_VERSION 32
 
 #define YR_ERR_UNSUPPORTED (-1) /* embedding width / option not compiled in   */
 #define YR_ERR_BADARG      (-2) /* null pointer, negative size, misalignment  */
@@ -221,6 +221,16 @@ int yr_bpr_mf_pull_apply(const float *U_old, float *U_new, float *I,
  * short.  Popularity is a property of the data set, so one order (e.g. from the train set's item degrees) serves
  * every step.  Results do not depend on it.  Ignored (as NULL) when the call covers only part of the item rows. */
 int yr_bpr_mf_pull_item_buckets(int64_t num_items, int D);
+/* yr_bpr_mf_pull_split_summary: which item buckets the partition in `workspace` shares between workgroups, for
+ * tests and measurement scripts (valid once the user phase of yr_bpr_mf_pull_apply has run for the batch; the call
+ * waits for `stream`).  counters_out[4] = {tile-range tasks, scratch slots, row tasks} the batch wants (word 3
+ * unused); parts_out[item buckets]: 1 = whole, P > 1 = P parts by tile range, -S = rows shared by S parts (in
+ * force only while the counters lie inside their pools).  rule_out[8] = the thresholds in force for (B, num_items,
+ * D): {tile split from, records per tile part, row split from, records per row part, four row parts from, most row
+ * parts, row-task pool, 1 if the row split is compiled in}.  workspace NULL (with both outputs NULL): the rule only. */
+int yr_bpr_mf_pull_split_summary(const void *workspace, int64_t workspace_bytes, int64_t B, int D,
+                                 int64_t num_users, int64_t num_items, int32_t *counters_out,
+                                 int32_t *parts_out, int32_t *rule_out, void *stream);
 int yr_bpr_mf_pull_apply_ordered(const float *U_old, float *U_new, float *I,
                          float *mU, float *vU, float *mI, float *vI, float *gradI_out,
                          int64_t B, int D, int64_t num_users, int64_t num_items, float inv_batch,

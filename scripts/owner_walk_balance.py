@@ -12,10 +12,14 @@ wave.  For every bucket this prints the walk iterations of the slowest wave unde
           --deal-min * (R / 16)^2 records keeps the index order                         (deal_rows in bpr_pull.hip)
   floor   the light records in four equal quarters
 
-and the records per bucket and per row.  The model takes a bucket's records in triplet order and cuts them every CAP
+and the records per bucket and per row.  With --row-split MIN TARGET it also models the item buckets whose ROWS are
+shared by S = 2 or 4 workgroups (YR_ROWSPLIT: buckets from max(MIN, AVG_MIN x the average bucket) records up and below the
+tile-range threshold; part q keeps the rows r with (r & (S - 1)) == q of every chunk of the whole bucket and deals and
+walks them as a bucket of its own): the workgroup count and the slowest-wave iterations per workgroup.  The model takes a bucket's records in triplet order and cuts them every CAP
 records (the kernel takes them tile by tile, which is the same order up to the arrangement inside a tile).
 
     python scripts/owner_walk_balance.py --bench [--batch 524288]     # step 0 of bench.py's batch pool (needs the GPU)
+    python scripts/owner_walk_balance.py --bench --row-split 1024 512  # ... and the row parts at these thresholds
     python scripts/owner_walk_balance.py --npz batch.npz --users N --items M   # arrays u, p, n
 """
 import argparse
@@ -92,6 +96,50 @@ def side_table(name, row_ids, n_rows, R, cap, heavy_t, per_iter, out, deal_min=0
     return res, per_bucket
 
 
+def row_split_table(row_ids, n_rows, R, cap, heavy_t, per_iter, deal_min, rule, whole, out):
+    """rule = (min, target, avg_min, avg_target, tile_min): the sizing of build_splits on this batch; whole = the dealt
+    slowest-wave iterations of every bucket taken whole (side_table)"""
+    mn, target, avg_min, avg_target, tile_min = rule
+    nb = (n_rows + R - 1) // R
+    avg = len(row_ids) / nb
+    mn, target = max(mn, int(avg_min * avg)), max(target, int(avg_target * avg))
+    tile_min = max(tile_min, int(2.5 * avg))
+    max_parts = 2 if R < 16 else 4
+    order = np.argsort(row_ids // R, kind="stable")
+    srt = row_ids[order]
+    bounds = np.searchsorted(srt // R, np.arange(nb + 1))
+    its, split, parts_n = [], 0, 0
+    for k in range(nb):
+        rows = srt[bounds[k]:bounds[k + 1]] % R
+        tot = len(rows)
+        if tot < mn or tot >= tile_min:
+            its.append(whole[k])
+            continue
+        S = 4 if (tot >= 3 * target and max_parts >= 4) else 2
+        split += 1
+        parts_n += S - 1
+        for q in range(S):
+            mine = (rows & (S - 1)) == q
+            wave, slot = np.zeros(4), None
+            for c0 in range(0, tot, cap):                 # chunks are cut on ALL records of the bucket
+                ch = rows[c0:c0 + cap][mine[c0:c0 + cap]]
+                cnt = np.bincount(ch, minlength=R)
+                heavy = cnt > heavy_t
+                hv = sum(-(-int(c) // (4 * per_iter)) for c in cnt[heavy])
+                light = np.where(heavy, 0, cnt)
+                if slot is None:
+                    slot = deal(cnt, R // 4, heavy_t) if cnt.sum() >= deal_min * R * R // 256 else np.arange(R)
+                wave += np.ceil(np.bincount(slot // (R // 4), weights=light, minlength=4) / per_iter) + hv
+            its.append(wave.max())
+    its = np.array(its)
+    pc = lambda a, q: float(np.percentile(a, q))
+    print(f"-- rows shared from {mn} records up (below {tile_min}), parts of about {target}: {split} buckets split, "
+          f"{nb + parts_n} workgroups (+{parts_n})", file=out)
+    print("slowest-wave walk iterations per workgroup   mean    p50    p90    p99    max", file=out)
+    for tag, a in (("whole buckets (dealt)", np.asarray(whole)), ("with row parts", its)):
+        print(f"  {tag:40s} {a.mean():6.2f} {pc(a, 50):6.0f} {pc(a, 90):6.0f} {pc(a, 99):6.0f} {a.max():6.0f}", file=out)
+
+
 def bench_batch(batch):
     """step 0 of bench.py's single-GPU batch pool"""
     import torch
@@ -117,6 +165,9 @@ def main():
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--heavy-row", type=int, default=96)
     ap.add_argument("--deal-min", type=int, default=256, help="YR_DEAL_MIN: first-chunk records (at 16-row buckets) from which rows are dealt")
+    ap.add_argument("--row-split", type=int, nargs=2, metavar=("MIN", "TARGET"),
+                    help="YR_ROWSPLIT_MIN / _TARGET: model the item buckets whose rows are shared by 2 or 4 workgroups")
+    ap.add_argument("--row-split-avg", type=float, nargs=2, default=(2.32, 1.16), metavar=("AVG_MIN", "AVG_TARGET"))
     ap.add_argument("--item-unroll", type=int, default=2)
     ap.add_argument("--user-unroll", type=int, default=1)
     args = ap.parse_args()
@@ -132,7 +183,10 @@ def main():
     print(f"# batch of {len(u)} triplets, {nu} users x {ni} items, D = {args.dim}")
     # item records in triplet order: the positive and the negative occurrence of every triplet
     items = np.stack([p, n], 1).reshape(-1)
-    side_table("item", items, ni, R, 1024, args.heavy_row, gpw * args.item_unroll, sys.stdout, args.deal_min)
+    res, _ = side_table("item", items, ni, R, 1024, args.heavy_row, gpw * args.item_unroll, sys.stdout, args.deal_min)
+    if args.row_split:
+        row_split_table(items, ni, R, 1024, args.heavy_row, gpw * args.item_unroll, args.deal_min,
+                        (*args.row_split, *args.row_split_avg, 2048), res[:, 1], sys.stdout)
     if (nu + R - 1) // R >= 768:      # below: one row per wave, nothing to deal
         side_table("user", np.asarray(u), nu, R, 768, args.heavy_row, gpw * args.user_unroll, sys.stdout, args.deal_min)
 

@@ -40,6 +40,8 @@
 //        occurrence, acc = sum g * U_old[user], I[i] = Adam(I[i], acc) (or the dense gradient rows
 //        for the multi-GPU all-reduce); workgroup 0 also reduces the loss partials of launch 2
 //        (fixed order) into the step loss and the running epoch loss.
+//        Item buckets far above the average are shared between workgroups: by tile range with a combine (oversize
+//        buckets, see kSplitMin) or, below that, by ROW without one (heavy buckets, see YR_ROWSPLIT).
 // The user table is double-buffered (U -> U_new) because the item pass needs the OLD user rows;
 // the item table is updated in place (a row is read only by its own lane group).
 //
@@ -88,6 +90,29 @@ constexpr int kSplitTarget = YR_SPLIT_TARGET;    // records per part (one chunk 
 constexpr int kMaxParts = 64;
 constexpr int kMaxTasks = 512;                   // helper workgroups at the front of the item pass's grid
 constexpr int kMaxSlots = 1024;                  // scratch slots of 1024 floats (one bucket's rows)
+// Heavy item buckets below that size (a few hundred buckets of two to three times the average one, whose owners end
+// the item pass long after the rest): the bucket's ROWS are shared out between S = 2 or 4 workgroups, the owner
+// (part 0) and S - 1 row helpers.  Part q finishes the local rows r with (r & (S - 1)) == q: every part reads the
+// whole bucket, drops the records of the other parts' rows while it loads them, and updates its own rows.  The parts
+// write disjoint rows: no scratch slot, no arrival counter, no fence, no atomic.
+#ifndef YR_ROWSPLIT
+#define YR_ROWSPLIT 1                 // 0: compiled out (no bucket is split by row, no row helper in the grid)
+#endif
+#ifndef YR_ROWSPLIT_MIN
+#define YR_ROWSPLIT_MIN 1024
+#endif
+#ifndef YR_ROWSPLIT_AVG_MIN
+#define YR_ROWSPLIT_AVG_MIN 2.32
+#endif
+#ifndef YR_ROWSPLIT_TARGET
+#define YR_ROWSPLIT_TARGET 512
+#endif
+#ifndef YR_ROWSPLIT_AVG_TARGET
+#define YR_ROWSPLIT_AVG_TARGET 1.16
+#endif
+constexpr int kRowSplitMin = YR_ROWSPLIT_MIN;        // records of a bucket from which its rows are shared out
+constexpr int kRowSplitTarget = YR_ROWSPLIT_TARGET;  // records per row part
+constexpr int kMaxRowTasks = YR_ROWSPLIT ? 512 : 0;  // entries of the row-task list (served by the free helper workgroups)
 constexpr int kBuildLanes = 4;                   // lanes that share one item bucket in the sizing workgroups of the USER pass
 #ifndef YR_DEAL
 #define YR_DEAL 1                     // 0: wave w finishes rows [w RPW, (w + 1) RPW) of its bucket (measurement only)
@@ -152,7 +177,7 @@ __global__ __launch_bounds__(kPartThreads) void tile_partition_kernel(
   // the split block of this batch starts clean: no tasks, no slots, every item bucket whole (the user pass's sizing
   // workgroups overwrite it; an item pass run without them must not meet the previous batch's parts)
   if (side == 0 && tile == 0) {
-    if (tid < 2) split_counters[tid] = 0;
+    if (tid < 3) split_counters[tid] = 0;     // tasks, slots, row tasks
     for (int i = tid; i < nbI; i += kPartThreads) split_counters[4 + i] = 1;
   }
   const int nb = side ? nbI : nbU;
@@ -278,10 +303,12 @@ struct OwnerArgs {
   int heavy_t;               // rows with more records in a chunk are walked by all four waves
   float inv_batch;
   PullAdam adam;
-  // oversize item buckets (see kSplitMin): `split` = the bookkeeping block of the workspace — {tasks, slots}
-  // counters (16 B), then parts[nbI], slot[nbI], arrive[nbI] (each padded to 16 B), then the task list.
-  // Item pass: the first helper_blocks workgroups are helpers (task j); parts[k] > 1 marks a split bucket whose
-  // parts leave their sums in scratch slot slot[k] + part.  User pass: its last build_blocks workgroups fill the
+  // oversize item buckets (see kSplitMin): `split` = the bookkeeping block of the workspace — {tasks, slots, row
+  // tasks} counters (16 B), then parts[nbI], slot[nbI], arrive[nbI] (each padded to 16 B), then the task list and
+  // the row-task list.  Item pass: the first helper_blocks workgroups are helpers, of a tile-range task (task j) from
+  // the first one up and of a row task from the last one down; parts[k] > 1 marks a bucket split by tile range whose
+  // parts leave their sums in scratch slot slot[k] + part, parts[k] = -S < 0 a bucket whose rows are shared by S
+  // parts.  User pass: its last build_blocks workgroups fill the
   // block for the item pass that follows, from the item-side offsets b_off [T][b_nb + 1].
   // (One pointer instead of seven: the kernel arguments live in scalar registers, and the item pass has none to spare.)
   char* split;
@@ -289,6 +316,7 @@ struct OwnerArgs {
   const int32_t* b_off;
   int helper_blocks, build_blocks, b_nb;
   int b_split_min, b_split_target;   // records from which a bucket is split / per part (host: scaled with the batch)
+  int b_rowsplit_min, b_rowsplit_quad;   // records from which a bucket's rows are shared by 2 / by 4 parts (host)
 };
 
 // the pieces of the `split` block
@@ -298,6 +326,7 @@ __device__ __forceinline__ int32_t* split_parts(char* b) { return (int32_t*)(b +
 __device__ __forceinline__ int32_t* split_slot(char* b, int nbI) { return (int32_t*)(b + 16 + split_per(nbI)); }
 __device__ __forceinline__ int32_t* split_arrive(char* b, int nbI) { return (int32_t*)(b + 16 + 2 * split_per(nbI)); }
 __device__ __forceinline__ int4* split_tasks(char* b, int nbI) { return (int4*)(b + 16 + 3 * split_per(nbI)); }
+__device__ __forceinline__ int2* split_row_tasks(char* b, int nbI) { return (int2*)(split_tasks(b, nbI) + kMaxTasks); }
 
 // Sizing of the item buckets (first workgroups of the user pass): kBuildLanes lanes per bucket add up its records
 // over the tiles (lane j takes tiles j, j + kBuildLanes, ...), the group's first lane decides the parts; split
@@ -341,6 +370,17 @@ __device__ __forceinline__ void build_splits(const OwnerArgs& a, int builder) {
       if (first + q - 1 < kMaxTasks) split_tasks(a.split, a.b_nb)[first + q - 1] = make_int4(fits ? k : -1, q, 0, 0);
     if (!fits) parts = 1;
   }
+#if YR_ROWSPLIT
+  else if (total < a.b_split_min && total >= a.b_rowsplit_min) {
+    // rows shared out: S - 1 row tasks {bucket, part}.  As above the counter counts what the batch WANTS, and the
+    // item pass shares no bucket's rows when that is more than the pool holds (the entries past it are not written)
+    const int S = total >= a.b_rowsplit_quad ? 4 : 2;
+    const int first = atomicAdd(split_counters(a.split) + 2, S - 1);
+    for (int q = 1; q < S; ++q)
+      if (first + q - 1 < kMaxRowTasks) split_row_tasks(a.split, a.b_nb)[first + q - 1] = make_int2(k, q);
+    parts = -S;
+  }
+#endif
   split_parts(a.split)[k] = parts;
   split_slot(a.split, a.b_nb)[k] = slot;
   split_arrive(a.split, a.b_nb)[k] = 0;
@@ -514,6 +554,12 @@ __device__ __forceinline__ void walk_stream(const OwnerArgs& a, const unsigned s
   }
 }
 
+// row split: whether local row `row` is one of part `part` of a bucket with the parts word `parts` (-S: the rows
+// with (row & (S - 1)) == part; 1 or a tile-range split: every row)
+__device__ __forceinline__ bool row_kept(int row, int part, int parts) {
+  return !YR_ROWSPLIT || ((row ^ part) & max(-parts - 1, 0)) == 0;
+}
+
 template <int D, bool USER, bool FUSE_ADAM, bool DET, int RPWX = 0>
 __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(OwnerArgs a) {
   using G = PullGeom<D>;
@@ -559,7 +605,8 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
     build_splits(a, blockIdx.x);
     return;
   }
-  // item pass: the first hb workgroups are helpers of split buckets; user pass: the first hb are the sizing ones
+  // item pass: the first hb workgroups are helpers of split buckets (by tile range from the first one up, by row
+  // from the last one down); user pass: the first hb are the sizing ones
   const int hb = USER ? a.build_blocks : a.helper_blocks;
   const bool helper = !USER && (int)blockIdx.x < hb;
   const int owners = (int)gridDim.x - hb;
@@ -573,30 +620,60 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
        helper ? ks == (int)blockIdx.x : ks < a.bucket_end; ks += owners) {
     // workgroups start in slot order: the caller may put heavy buckets first (wave-uniform: kept in a scalar register)
     int k, part = 0, parts = 1;
+    // rows shared out (YR_ROWSPLIT): parts = -S < 0, and this workgroup keeps the local rows r with
+    // (r & (S - 1)) == part (see row_kept: a whole bucket and a part by tile range keep every row, so the load phase
+    // and the tail below have one form).  The two words that describe a tile-range part serve: the item pass has no
+    // further scalar register to spare, and every one it lacks costs it a vector register, which it lacks too
     // Which buckets are shared is a function of the batch alone: the sizing workgroups count every task and slot the
     // batch WANTS (their sums do not depend on arrival order); a batch that wants more than the pools hold shares no
     // bucket at all — every bucket is summed whole, the helpers leave at once.  (Which buckets had found room
     // depended on the order of two global atomics; a whole and a shared bucket add in different orders.)
-    const bool pools_hold = USER || !a.split || (split_counters(a.split)[0] <= kMaxTasks &&
-                                                 split_counters(a.split)[1] <= kMaxSlots);   // two scalar loads
-    if (helper) {
-      if (!pools_hold || ks >= split_counters(a.split)[0]) break;
+    // (the counter block in ONE 16-byte load, and the owner's bucket before either is waited for: every load of this
+    // prologue is a round trip to the L2 that the whole workgroup waits for)
+    int4 cnt = make_int4(0, 0, 0, 0);
+    if (!USER && a.split) cnt = *reinterpret_cast<const int4*>(a.split);
+    int k_own = ks;
+    if (!helper && a.order) k_own = a.order[ks];
+    const int c_tasks = __builtin_amdgcn_readfirstlane(cnt.x), c_slots = __builtin_amdgcn_readfirstlane(cnt.y);
+    const int c_rows = __builtin_amdgcn_readfirstlane(cnt.z);
+    const bool pools_hold = USER || !a.split || (c_tasks <= kMaxTasks && c_slots <= kMaxSlots);
+    // The same rule for the row tasks, with a list, a counter and a pool of their own.  They are served by the helper
+    // workgroups the tile-range tasks leave free, from the last one down (row task j by helper kMaxTasks - 1 - j: 512
+    // more workgroups that find nothing to do cost every step 1 us, measured), so both kinds must fit into them
+    const int tile_tasks = (USER || !a.split || !pools_hold) ? 0 : c_tasks;
+    const bool rows_hold = !USER && YR_ROWSPLIT && a.split && c_rows <= kMaxRowTasks && tile_tasks + c_rows <= kMaxTasks;
+    const bool row_helper = YR_ROWSPLIT && helper && ks >= tile_tasks;
+    if (row_helper) {
+      const int j = kMaxTasks - 1 - ks;
+      if (!rows_hold || j >= c_rows) break;
+      const int2 task = split_row_tasks(a.split, a.nb)[j];
+      k = __builtin_amdgcn_readfirstlane(task.x);
+      part = __builtin_amdgcn_readfirstlane(task.y);
+      if (k < a.bucket_begin || k >= a.bucket_end) break;       // a bucket of another item chunk
+    } else if (helper) {
+      if (ks >= tile_tasks) break;
       const int4 task = split_tasks(a.split, a.nb)[ks];
       k = __builtin_amdgcn_readfirstlane(task.x);
       part = __builtin_amdgcn_readfirstlane(task.y);
       if (k < a.bucket_begin || k >= a.bucket_end) break;       // void task, or a bucket of another item chunk
     } else {
-      k = __builtin_amdgcn_readfirstlane(a.order ? a.order[ks] : ks);
+      k = __builtin_amdgcn_readfirstlane(k_own);
     }
-    if (!USER && a.split && pools_hold) parts = __builtin_amdgcn_readfirstlane(split_parts(a.split)[k]);
+    if (!USER && a.split) {
+      const int word = __builtin_amdgcn_readfirstlane(split_parts(a.split)[k]);
+      if (word > 1 && pools_hold) parts = word;
+      if (YR_ROWSPLIT && word < 0 && rows_hold) parts = word;
+    }
+    if (row_helper && parts >= 0) break;         // a row task without its bucket's word: never
     // this workgroup's share of the bucket: the tiles [t_begin, t_end)
     // (an integer division runs on the vector unit: the results are moved back to scalar registers, or they would
     // cost the item pass two VGPRs it does not have — 12 B of scratch per lane, caught by scripts/kernel_resources.py)
-    const int t_begin = __builtin_amdgcn_readfirstlane(a.T * part / parts);
-    const int t_end = __builtin_amdgcn_readfirstlane(a.T * (part + 1) / parts);
+    // (a row part reads every tile)
+    const int t_begin = parts < 0 ? 0 : __builtin_amdgcn_readfirstlane(a.T * part / parts);
+    const int t_end = parts < 0 ? a.T : __builtin_amdgcn_readfirstlane(a.T * (part + 1) / parts);
     int row_t = row_l;                           // the local row this lane group finishes
     int row_f = k * R + row_t;
-    bool valid_f = finisher && row_f < a.rows;
+    bool valid_f = finisher && row_f < a.rows && (USER || row_kept(row_t, part, parts));
     uint32_t o_f = (uint32_t)(row_f * D + 4 * l);
     // DEAL: the binding of rows to slots is fixed by the first chunk that holds a record and kept for the bucket
     // (the register totals persist over chunks, tile groups and windows); workgroup-uniform
@@ -682,7 +759,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
             } else {
               const int2 oc = static_cast<const int2*>(a.recs)[rbase + sidx];
               const uint32_t b = (uint32_t)(oc.y & 0x7fffffff);
-              if (b - id_lo < (uint32_t)W) {
+              if (b - id_lo < (uint32_t)W && row_kept((int)((uint32_t)oc.x >> kOccShift), part, parts)) {
                 const float g = a.coeff[b];
                 const int slot = atomicAdd(&s_n, 1);
                 s_x[slot] = oc.x & kOccMask;
@@ -741,6 +818,11 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
 #pragma unroll
           for (int q = 0; q < PT; ++q)
             oc[q] = *reinterpret_cast<const int2*>(static_cast<const char*>(a.recs) + (uint32_t)(addr[q] * 8u));
+          // records of another part's rows are dropped here: their coefficient load reads index 0, and the counts,
+          // the deal, the stream and the heavy rows below see the kept records only
+#pragma unroll
+          for (int q = 0; q < PT; ++q)
+            if (!row_kept((int)((uint32_t)oc[q].x >> kOccShift), part, parts)) key[q] = -1;
 #pragma unroll
           for (int q = 0; q < PT; ++q) {
             const uint32_t b = key[q] >= 0 ? (uint32_t)(oc[q].y & 0x7fffffff) : 0u;
@@ -766,7 +848,14 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
             // step takes 16 R records off the stream: a first chunk with few records (a short walk: nothing to win
             // back) keeps the identity.  The bar grows with R * R — 64 records at D = 128, 256 at D = 64, a full item
             // chunk at D = 32 (DEAL is off where no chunk can reach it)
-            if (n_rec >= DEAL_BAR) {
+            // (a row part: what counts is what it kept)
+            int n_deal = n_rec;
+            if (!USER && YR_ROWSPLIT && parts < 0) {
+              n_deal = s_cnt[lane];
+#pragma unroll
+              for (int m = 1; m < kWave; m <<= 1) n_deal += __shfl_xor(n_deal, m, kWave);
+            }
+            if (n_deal >= DEAL_BAR) {
               deal_rows<R, RPW>(s_cnt, s_slotof, s_rowof, lane, a.heavy_t);
             } else {
               s_slotof[lane] = (unsigned char)lane;
@@ -784,10 +873,12 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
           const int total_light = __shfl(il, kWave - 1, kWave);
           s_light[lane] = il - cl;
           if (lane == kWave - 1) s_light[kWave] = il;
+          if (!USER && YR_ROWSPLIT && lane == kWave - 1) s_n = il + ih;   // records in the stream (a row part: the kept ones)
           s_start[row] = heavy ? total_light + ih - ch : il - cl;
         }
         bound = true;
         __syncthreads();
+        if (!USER && YR_ROWSPLIT && parts < 0) n_rec = __builtin_amdgcn_readfirstlane(s_n);   // gates the re-ranking and the heavy rows below
 #pragma unroll
         for (int q = 0; q < PT; ++q)
           if (key[q] >= 0) {
@@ -866,7 +957,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
     if (DEAL) {                                  // the row this slot was dealt (a bucket without records: the identity)
       if (bound) row_t = s_rowof[row_l];
       row_f = k * R + row_t;
-      valid_f = row_f < a.rows;
+      valid_f = row_f < a.rows && (USER || row_kept(row_t, part, parts));
       // (the lane's column offset is taken afresh from the thread index, through an empty asm: otherwise 4 * l is kept
       // over the whole walk for this one use — the register the D = 128 user pass then lacks went to scratch memory)
       int t2 = tid;
@@ -882,7 +973,12 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
       asm volatile("" : "+s"(sbase));
       float* slots = sbase + (int64_t)split_slot(a.split, a.nb)[k] * (R * D);
       // slots are indexed by the TRUE local row: every part deals its own rows
-      if (finisher) st4(slots + (int64_t)part * (R * D) + row_t * D + 4 * l, acc);
+      // (the lane's column is taken afresh from the thread index here too: kept from the kernel's start for this
+      // rare path, it was the register pair the fused D = 64 form went to scratch memory for)
+      int t3 = tid;
+      asm volatile("" : "+v"(t3));
+      const int lc = 4 * (t3 % LPR);
+      if (finisher) st4(slots + (int64_t)part * (R * D) + row_t * D + lc, acc);
       __threadfence();
       __syncthreads();
       if (tid == 0) {
@@ -898,7 +994,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
       acc = zero4();
       if (finisher) {
         for (int q = 0; q < parts; ++q) {
-          const float4 t = ld4(slots + (int64_t)q * (R * D) + row_t * D + 4 * l);
+          const float4 t = ld4(slots + (int64_t)q * (R * D) + row_t * D + lc);
           acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
         }
       }
@@ -972,9 +1068,11 @@ struct PullPlan {
   int pt, tile, T, shiftU, shiftI, narrow_users, nbU, nbI;
   size_t o_offU, o_offI, o_rec, o_occ, o_coeff, o_split, o_scratch, bytes;
 };
-// split bookkeeping inside the workspace: {tasks, slots} counters (16 B), parts / slot / arrivals per item bucket,
-// the task list; then the scratch slots
-inline size_t split_bytes(int nbI) { return 16 + (size_t)3 * align16((size_t)nbI * 4) + (size_t)kMaxTasks * sizeof(int4); }
+// split bookkeeping inside the workspace: {tasks, slots, row tasks} counters (16 B), parts / slot / arrivals per item
+// bucket, the task list, the row-task list; then the scratch slots
+inline size_t split_bytes(int nbI) {
+  return 16 + (size_t)3 * align16((size_t)nbI * 4) + (size_t)kMaxTasks * sizeof(int4) + (size_t)kMaxRowTasks * sizeof(int2);
+}
 
 // tiles of 4096 triplets, halved while there would be fewer than kMinTiles of them (the partition launch
 // and the owners' segment runs both want tiles that are neither too few nor too small)
@@ -1010,6 +1108,28 @@ inline PullPlan make_plan(int64_t B, int64_t nU, int64_t nI, int D, bool upper_b
   p.o_scratch = o; o += (size_t)kMaxSlots * 1024 * 4;
   p.bytes = o;
   return p;
+}
+
+// Which item buckets are shared, for a batch of B triplets.  By tile range: oversize = well above the average bucket
+// of THIS batch (2B occurrences over nbI buckets), and never below the floors: at one epoch per step the average
+// bucket already holds 770 records.  By row (below that): the same rule with floors and multiples of its own; two
+// parts up to three times the target, four from there on where a part then keeps at least four rows (D <= 64).
+struct SplitRule {
+  int split_min, split_target, row_min, row_target, row_quad, row_max_parts;
+};
+inline SplitRule split_rule(int64_t B, int nbI, int D) {
+  SplitRule r;
+  const double avg = 2.0 * (double)B / (double)nbI;
+  const int by_avg_min = (int)(YR_SPLIT_AVG_MIN * avg), by_avg_target = (int)(YR_SPLIT_AVG_TARGET * avg);
+  r.split_min = by_avg_min > kSplitMin ? by_avg_min : kSplitMin;
+  r.split_target = by_avg_target > kSplitTarget ? by_avg_target : kSplitTarget;
+  const int row_avg_min = (int)(YR_ROWSPLIT_AVG_MIN * avg), row_avg_target = (int)(YR_ROWSPLIT_AVG_TARGET * avg);
+  r.row_min = row_avg_min > kRowSplitMin ? row_avg_min : kRowSplitMin;
+  r.row_target = row_avg_target > kRowSplitTarget ? row_avg_target : kRowSplitTarget;
+  r.row_max_parts = D == 128 ? 2 : 4;
+  r.row_quad = r.row_max_parts >= 4 && r.row_target < 0x7fffffff / 3 ? 3 * r.row_target : 0x7fffffff;
+  if (!YR_ROWSPLIT) { r.row_min = 0x7fffffff; r.row_quad = 0x7fffffff; r.row_max_parts = 1; }
+  return r;
 }
 
 }  // namespace yr
@@ -1110,14 +1230,9 @@ static int pull_apply_impl(const float* U_old, float* U_new, float* I, float* mU
     // the last kSplitBuilders workgroups size the item buckets (oversize ones are shared out in the item pass)
     ua.build_blocks = (p.nbI * kBuildLanes + kBlock - 1) / kBlock;
     ua.b_off = (const int32_t*)(w + p.o_offI); ua.b_nb = p.nbI;
-    {
-      // oversize = well above the average bucket of THIS batch (2B occurrences over nbI buckets), and never below
-      // the floors: at one epoch per step the average bucket already holds 770 records
-      const double avg = 2.0 * (double)B / (double)p.nbI;
-      const int by_avg_min = (int)(YR_SPLIT_AVG_MIN * avg), by_avg_target = (int)(YR_SPLIT_AVG_TARGET * avg);
-      ua.b_split_min = by_avg_min > kSplitMin ? by_avg_min : kSplitMin;
-      ua.b_split_target = by_avg_target > kSplitTarget ? by_avg_target : kSplitTarget;
-    }
+    const SplitRule rule = split_rule(B, p.nbI, D);
+    ua.b_split_min = rule.split_min; ua.b_split_target = rule.split_target;
+    ua.b_rowsplit_min = rule.row_min; ua.b_rowsplit_quad = rule.row_quad;
     ua.split = w + p.o_split;
     const int gu = (p.nbU < YR_LOSS_PARTIALS ? p.nbU : YR_LOSS_PARTIALS) + ua.build_blocks;   // one loss-partial slot per owner
     if (p.narrow_users && deterministic)
@@ -1147,7 +1262,7 @@ static int pull_apply_impl(const float* U_old, float* U_new, float* I, float* mU
     ia.scratch = (float*)(w + p.o_scratch);
     int gi = ia.bucket_end - ia.bucket_begin;
     if (gi > kMaxOwnerGrid) gi = kMaxOwnerGrid;
-    gi += kMaxTasks;                              // helpers first: they start before the owners
+    gi += ia.helper_blocks;                       // helpers first: they start before the owners
     if (gradI_out && deterministic)
       hipLaunchKernelGGL((owner_pass_kernel<D, false, false, true>), dim3(gi), dim3(kBlock), 0, s, ia);
     else if (gradI_out)
@@ -1167,6 +1282,30 @@ extern "C" int yr_bpr_mf_pull_item_buckets(int64_t num_items, int D) {
   if (num_items <= 0 || (D != 16 && D != 32 && D != 64 && D != 128)) return YR_ERR_BADARG;
   const int sh = bucket_shift(D);
   return (int)((num_items + (1 << sh) - 1) >> sh);
+}
+
+// What build_splits decided for the partition in `workspace` (tests and measurement scripts; synchronises `stream`).
+extern "C" int yr_bpr_mf_pull_split_summary(const void* workspace, int64_t workspace_bytes, int64_t B, int D,
+                                            int64_t num_users, int64_t num_items, int32_t* counters_out,
+                                            int32_t* parts_out, int32_t* rule_out, void* stream) {
+  if (!rule_out || B <= 0 || num_users <= 0 || num_items <= 0) return YR_ERR_BADARG;
+  if (D != 16 && D != 32 && D != 64 && D != 128) return YR_ERR_UNSUPPORTED;
+  const PullPlan p = make_plan(B, num_users, num_items, D, false);
+  const SplitRule r = split_rule(B, p.nbI, D);
+  const int32_t rule[8] = {r.split_min, r.split_target, r.row_min, r.row_target, r.row_quad, r.row_max_parts,
+                           kMaxRowTasks, YR_ROWSPLIT};
+  for (int i = 0; i < 8; ++i) rule_out[i] = rule[i];
+  if (!workspace) return (counters_out || parts_out) ? YR_ERR_BADARG : 0;
+  const int rc = pull_check_common(B, D, num_users, num_items, workspace, workspace_bytes);
+  if (rc) return rc;
+  const char* blk = static_cast<const char*>(workspace) + p.o_split;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipSuccess;
+  if (counters_out) e = hipMemcpyAsync(counters_out, blk, 16, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && parts_out)
+    e = hipMemcpyAsync(parts_out, blk + 16, (size_t)p.nbI * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return (int)e;
 }
 
 extern "C" int yr_bpr_mf_pull_apply_ordered(const float* U_old, float* U_new, float* I, float* mU, float* vU,

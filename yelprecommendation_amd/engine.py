@@ -158,6 +158,39 @@ def bpr_mf_pull_workspace(max_batch, num_users, num_items, d, device):
     return torch.empty(int(n), dtype=torch.uint8, device=device)
 
 
+PULL_RULE_FIELDS = ("split_min", "split_target", "row_min", "row_target", "row_quad", "row_max_parts",
+                    "row_task_pool", "row_split_compiled")
+
+
+def bpr_mf_pull_split_summary(batch, num_users, num_items, d, workspace=None):
+    """Which item buckets the pull step shares between workgroups (yr_bpr_mf_pull_split_summary), for tests and
+    measurement scripts.  Returns a dict: the thresholds in force for (batch, num_items, d) under the names of
+    ``PULL_RULE_FIELDS`` and, with the ``workspace`` of a partition whose user phase has run (one device sync),
+    ``tasks`` / ``slots`` / ``row_tasks`` (what the batch wants) and ``parts`` (int32 array per item bucket:
+    1 whole, P > 1 parts by tile range, -S rows shared by S parts)."""
+    import ctypes
+    import numpy as np
+    lib = _lib.load()
+    rule = (ctypes.c_int32 * 8)()
+    counters = (ctypes.c_int32 * 4)()
+    nb = int(lib.yr_bpr_mf_pull_item_buckets(int(num_items), int(d)))
+    if nb < 0:
+        check(nb, "yr_bpr_mf_pull_item_buckets")
+    parts = np.zeros(nb, np.int32)
+    if workspace is None:
+        rc = lib.yr_bpr_mf_pull_split_summary(None, 0, int(batch), int(d), int(num_users), int(num_items), None, None,
+                                              rule, None)
+    else:
+        rc = lib.yr_bpr_mf_pull_split_summary(workspace.data_ptr(), workspace.numel(), int(batch), int(d),
+                                              int(num_users), int(num_items), counters, parts.ctypes.data, rule,
+                                              _stream())
+    check(rc, "yr_bpr_mf_pull_split_summary")
+    out = dict(zip(PULL_RULE_FIELDS, (int(v) for v in rule)))
+    if workspace is not None:
+        out.update(tasks=int(counters[0]), slots=int(counters[1]), row_tasks=int(counters[2]), parts=parts)
+    return out
+
+
 def bpr_mf_pull_step(U_old, U_new, I, mU, vU, mI, vI, user, pos, neg, step, lr, loss_partials, workspace,
                      beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, decoupled=False, inv_batch=None,
                      gradI_out=None, err_flag=None, loss_out=None, loss_accum=None, deterministic=False):
