@@ -1,7 +1,8 @@
 """GPU parity for DCN: the input assembly (forward / scatter backward / bad ids), the ReLU epilogue of yr_gemm_f32,
 the fused head against float64 autograd of the reference's einsum form, a whole training step and a trainer replay
 against the reference's capture (tests/golden/dcn_small.npz), the fused catalogue scorer against float64 and against
-an unfused GPU route at Yelp2018 shape, checkpoints, and the shapes the kernels refuse."""
+an unfused GPU route at Yelp2018 shape, checkpoints, and the shapes the kernels refuse.
+The loop ends of every kernel, element by element against float64: tests/test_gpu_dcn_edges.py."""
 import os
 
 import numpy as np
