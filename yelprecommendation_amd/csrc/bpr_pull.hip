@@ -124,6 +124,14 @@ constexpr int kDealMin = YR_DEAL_MIN;            // records in a bucket's first 
 #ifndef YR_OWNER_WAVES
 #define YR_OWNER_WAVES 8              // waves per SIMD the owner pass is compiled for (8 workgroups per CU: <= 64 VGPRs)
 #endif
+#ifndef YR_USER_UNROLL
+#define YR_USER_UNROLL 1
+#endif
+#ifndef YR_ITEM_UNROLL
+#define YR_ITEM_UNROLL 2
+#endif
+constexpr int kUserUnroll = YR_USER_UNROLL;   // steps in flight per lane group; two gathered rows per contribution
+constexpr int kItemUnroll = YR_ITEM_UNROLL;
 
 struct PullAdam {
   AdamScalars c;
@@ -308,7 +316,7 @@ struct OwnerArgs {
   // the row-task list.  Item pass: the first helper_blocks workgroups are helpers, of a tile-range task (task j) from
   // the first one up and of a row task from the last one down; parts[k] > 1 marks a bucket split by tile range whose
   // parts leave their sums in scratch slot slot[k] + part, parts[k] = -S < 0 a bucket whose rows are shared by S
-  // parts.  User pass: its last build_blocks workgroups fill the
+  // parts.  User pass: its first build_blocks workgroups fill the
   // block for the item pass that follows, from the item-side offsets b_off [T][b_nb + 1].
   // (One pointer instead of seven: the kernel arguments live in scalar registers, and the item pass has none to spare.)
   char* split;
@@ -466,15 +474,8 @@ __device__ __forceinline__ void deal_rows(const int* s_cnt, unsigned char* s_slo
   s_rowof[slot] = (unsigned char)lane;
 }
 
-#ifndef YR_USER_UNROLL
-#define YR_USER_UNROLL 1
-#endif
-#ifndef YR_ITEM_UNROLL
-#define YR_ITEM_UNROLL 2
-#endif
-constexpr int kUserUnroll = YR_USER_UNROLL;   // steps in flight per lane group; two gathered rows per contribution
-constexpr int kItemUnroll = YR_ITEM_UNROLL;
 constexpr int kTagShift = 10;    // s_idx entry = load-order index (< kCap) | local row << 10
+constexpr int kTagMask = (1 << kTagShift) - 1;
 
 // One pass of a wave over the stream positions lo + first + k * stride < hi (sorted by row); books
 // row sums into `sums` (slots relative to `row_base`; LOOKUP: the entries are tagged with rows, whose slot is looked
@@ -502,7 +503,7 @@ __device__ __forceinline__ void walk_stream(const OwnerArgs& a, const unsigned s
       valid[q] = pos < hi;
       const int e = s_idx[min(pos, hi - 1)];                    // past the end: the last record, weight 0
       tag[q] = e >> kTagShift;
-      const int c = e & ((1 << kTagShift) - 1);
+      const int c = e & kTagMask;
       ia[q] = s_x[c];
       ib[q] = s_y[c];
       ic[q] = USER ? s_z[c] : 0;
@@ -560,23 +561,257 @@ __device__ __forceinline__ bool row_kept(int row, int part, int parts) {
   return !YR_ROWSPLIT || ((row ^ part) & max(-parts - 1, 0)) == 0;
 }
 
-template <int D, bool USER, bool FUSE_ADAM, bool DET, int RPWX = 0>
-__global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(OwnerArgs a) {
-  using G = PullGeom<D>;
-  constexpr int LPR = G::LPR, GPW = G::GPW;
-  constexpr int RPW = RPWX ? RPWX : GPW;         // rows a wave owns (RPWX = 0: one per lane group)
+// steps of one walk_stream call over n records taken `groups` at a time (instrumented builds count them)
+template <bool USER>
+__device__ __forceinline__ int walk_steps(int n, int groups) {
+  const int per = groups * (USER ? kUserUnroll : kItemUnroll);
+  return (n + per - 1) / per;
+}
+
+// --------------------------------------------------------------------------- the phases of an owner pass
+// owner_pass_kernel below is this sequence, per bucket (or part of a bucket) of its workgroup:
+//   bucket selection;  for tile groups: scan_segments;  for chunks: cut_chunk_at_tiles (DET), load_window (DET) or the
+//   plain loader, stream layout, rerank_by_id (DET), walk_stream over the light rows, the heavy-row loop;
+//   final row binding, leave_part_sums + sum_part_slots (a part by tile range), row update;  after the last bucket the loss.
+// The phases with a name are functions, inlined into the kernel; the others are delimited blocks of its body, because
+// as functions they changed the machine code of the forms the trainers run (profiles/owner_pass_phases_resources.txt
+// has every shape that was tried and what it did).  The kernel declares the LDS arrays (their order and sizes are its
+// layout) and hands them to the functions as pointers; a function gets every other value it works on as an argument,
+// and its comment says which of them must be uniform over the workgroup (it holds barriers that depend on them).
+
+// What one instance of the kernel is compiled for: the geometry and the paths its template arguments select.
+template <int D_, bool USER_, bool FUSE_ADAM_, bool DET_, int RPWX>
+struct OwnerForm {
+  static constexpr int D = D_;
+  static constexpr bool USER = USER_, FUSE_ADAM = FUSE_ADAM_, DET = DET_;
+  static constexpr int LPR = PullGeom<D>::LPR, GPW = PullGeom<D>::GPW;
+  static constexpr int RPW = RPWX ? RPWX : GPW;         // rows a wave owns (RPWX = 0: one per lane group)
   static_assert(RPW <= GPW, "a wave finishes at most one row per lane group");
-  constexpr int R = kWavesPerBlock * RPW;        // rows per bucket
-  constexpr int DEAL_BAR = kDealMin * (kWavesPerBlock * GPW) * (kWavesPerBlock * GPW) / 256;   // records in the first chunk
+  static constexpr int R = kWavesPerBlock * RPW;        // rows per bucket
+  static constexpr int DEAL_BAR = kDealMin * (kWavesPerBlock * GPW) * (kWavesPerBlock * GPW) / 256;   // records in the first chunk
   // rows dealt to the lane groups by load: not with one row per wave (nothing to deal), and not where a chunk can never
   // hold DEAL_BAR records (D = 16, the user side at D = 32): those forms compile to the index-order binding
-  constexpr bool DEAL = RPWX == 0 && YR_DEAL && DEAL_BAR <= (USER ? kUserCap : kCap);
+  static constexpr bool DEAL = RPWX == 0 && YR_DEAL && DEAL_BAR <= (USER ? kUserCap : kCap);
   // The tag of a stream entry names what the walk needs without a further lookup.  Item pass: the SLOT (the walk only
   // books sums, as it did before rows were dealt: it has no register to spare).  User pass: the local ROW (every
   // record reads the row's own embedding from s_own), and the slot is looked up when a row closes.
-  constexpr bool TAG_SLOT = DEAL && !USER, LOOKUP = DEAL && USER;
-  constexpr int CAP = USER ? kUserCap : kCap;    // records per chunk
-  constexpr int PT = CAP / kBlock;
+  static constexpr bool TAG_SLOT = DEAL && !USER, LOOKUP = DEAL && USER;
+  static constexpr int CAP = USER ? kUserCap : kCap;    // records per chunk
+  static constexpr int PT = CAP / kBlock;               // records per thread and chunk
+};
+
+// the kernel's LDS arrays that the phases below work on (see their declarations there); dissolved by the optimiser
+struct OwnerLds {
+  int *pre, *base, *cnt, *start;
+  unsigned char* rowof;
+  int *x, *y, *z;
+  unsigned short* idx;
+  int *scan, *n, *last;
+};
+
+// The tile whose segment holds flattened index j: the last of the nt tiles with s_pre[tile] <= j (a tile whose
+// segment STARTS at j wins over the empty ones before it).
+__device__ __forceinline__ int tile_of(const int* s_pre, int nt, int j) {
+  int tlo = 0, thi = nt;
+  while (thi - tlo > 1) {
+    const int mid = (tlo + thi) >> 1;
+    if (s_pre[mid] <= j) tlo = mid; else thi = mid;
+  }
+  return tlo;
+}
+
+// Segment descriptors of bucket k in the tiles [tg0, tg0 + nt), nt <= kTileGroup: s_base[i] = where tile tg0 + i's
+// segment sits in the record array, s_pre[0..nt] = exclusive scan of the segments' lengths.  Returns s_pre[nt], the
+// records of the tile group.  k, tg0 and nt are workgroup-uniform (one or two barriers; up to 64 tiles one wave
+// scans); writes s_base, s_pre, s_scan, and ends on a barrier.  tid = the thread of the workgroup, here and below.
+__device__ __forceinline__ int scan_segments(const OwnerArgs& a, const OwnerLds& s, int tid, int k, int tg0,
+                                             int nt) {
+  const int lane = tid & (kWave - 1), wave = tid / kWave;
+  int len = 0;
+  if (tid < nt) {
+    const int32_t* orow = a.off + (int64_t)(tg0 + tid) * (a.nb + 1) + k;
+    const int o0 = orow[0], o1 = orow[1];
+    len = o1 - o0;
+    s.base[tid] = (tg0 + tid) * a.tile_stride + o0;
+  }
+  int inc = 0, before = 0;
+  if (nt > kWave) {
+    inc = wave_inclusive_scan(len, lane);
+    if (lane == kWave - 1) s.scan[wave] = inc;
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) before += s.scan[w];
+  } else if (wave == 0) {                    // up to 64 tiles: one wave scans
+    inc = wave_inclusive_scan(len, lane);
+  }
+  if (nt > kWave || wave == 0) {
+    s.pre[tid] = before + inc - len;
+    if (lane == kWave - 1) s.pre[tid + 1] = before + inc;   // entry after a wave's last (the total after the last wave)
+  }
+  __syncthreads();
+  return s.pre[nt];
+}
+
+// DET: which records share a chunk must not depend on the (arbitrary) order inside a tile's segment.  Chunks
+// are cut at tile boundaries; a segment larger than a chunk is taken in WINDOWS of triplet ids (a window of
+// CAP ids holds at most CAP user-side records, one of CAP / 2 ids at most CAP item occurrences): every window
+// scans the whole segment and keeps what falls into it — a fixed set, ranked by triplet id in rerank_by_id.
+// Here: wt = the tile whose segment starts at c0 (chunks start at boundaries); returns whether that segment is
+// oversize (the chunk is one of its windows); otherwise cuts cend back to the last tile boundary after c0, if there
+// is one.  Reads s_pre; every argument is workgroup-uniform, and so are the results.
+template <int CAP>
+__device__ __forceinline__ bool cut_chunk_at_tiles(const int* s_pre, int nt, int c0, int total, int& cend, int& wt) {
+  wt = tile_of(s_pre, nt, c0);
+  const bool windowed = s_pre[wt + 1] - s_pre[wt] > CAP;
+  if (!windowed && cend < total) {
+    const int tb = tile_of(s_pre, nt, cend);
+    if (s_pre[tb] > c0) cend = s_pre[tb];
+  }
+  return windowed;
+}
+
+// DET, an oversize segment (tile tg0 + wt of the group): the records of id window `sub` go into s_x / s_y / s_z in
+// arrival order (s_n counts them, s_idx holds their local rows until the keys are taken), then every thread takes the
+// keys of its PT records, key = local row | rank inside the row << 8 (s_cnt), -1 for none.  Moves on to the next
+// window (sub + 1, cend = c0: the same segment again) or past the segment (sub = 0, cend = its end).  Returns the
+// records kept: 0 is possible, and the caller then skips the chunk.  Expects s_cnt and s_n zeroed behind a barrier;
+// one barrier inside.  part / parts (the rows this workgroup keeps), tg0, wt, c0, sub, cend are workgroup-uniform.
+template <class F>
+__device__ __forceinline__ int load_window(const OwnerArgs& a, const OwnerLds& s, int tid, int part,
+                                           int parts, int tg0, int wt, int c0, int& sub, int& cend,
+                                           int (&key)[F::PT]) {
+  constexpr bool USER = F::USER;
+  constexpr int CAP = F::CAP, PT = F::PT;
+  constexpr int W = USER ? CAP : CAP / 2;
+  const int tile_ids = USER ? a.tile_stride : a.tile_stride >> 1;
+  const int seg = s.pre[wt + 1] - s.pre[wt];
+  const uint32_t rbase = (uint32_t)s.base[wt];
+  const uint32_t id_lo = (uint32_t)(tg0 + wt) * (uint32_t)tile_ids + (uint32_t)sub * (uint32_t)W;
+  for (int sidx = tid; sidx < seg; sidx += kBlock) {
+    if (USER) {
+      const int4 r = static_cast<const int4*>(a.recs)[rbase + sidx];
+      if ((uint32_t)r.z - id_lo < (uint32_t)W) {
+        const int slot = atomicAdd(s.n, 1);
+        s.x[slot] = r.x; s.y[slot] = r.y; s.z[slot] = r.z;
+        s.idx[slot] = (unsigned short)r.w;     // the local row, until the keys below are taken
+      }
+    } else {
+      const int2 oc = static_cast<const int2*>(a.recs)[rbase + sidx];
+      const uint32_t b = (uint32_t)(oc.y & 0x7fffffff);
+      if (b - id_lo < (uint32_t)W && row_kept((int)((uint32_t)oc.x >> kOccShift), part, parts)) {
+        const float g = a.coeff[b];
+        const int slot = atomicAdd(s.n, 1);
+        s.x[slot] = oc.x & kOccMask;
+        s.y[slot] = __float_as_int(oc.y < 0 ? -g : g);
+        s.z[slot] = oc.y;
+        s.idx[slot] = (unsigned short)((uint32_t)oc.x >> kOccShift);
+      }
+    }
+  }
+  __syncthreads();
+  const int n_rec = *s.n;
+#pragma unroll
+  for (int q = 0; q < PT; ++q) {
+    const int c = tid + q * kBlock;
+    key[q] = -1;
+    if (c < n_rec) {
+      const int local = s.idx[c];
+      key[q] = local | (atomicAdd(&s.cnt[local], 1) << 8);
+    }
+  }
+  ++sub;                                       // the next window of this segment, or the next tile boundary
+  if (sub * W >= tile_ids) { sub = 0; cend = s.pre[wt + 1]; }
+  else cend = c0;
+  return n_rec;
+}
+
+// DET: the ranks inside a row came from LDS atomics in arrival order: re-rank every row of the stream by triplet id
+// (s_z; unique inside a row), so that the order of every floating-point sum of the walks is fixed.  Reads s_idx,
+// s_start, s_cnt, s_z (s_rowof), rewrites s_idx between two barriers.  n_rec = entries of the stream, workgroup-uniform.
+template <class F>
+__device__ __forceinline__ void rerank_by_id(const OwnerLds& s, int tid, int n_rec) {
+  constexpr int PT = F::PT;
+  int at[PT];
+  unsigned short ent[PT];
+#pragma unroll
+  for (int q = 0; q < PT; ++q) {
+    const int pos = tid + q * kBlock;
+    at[q] = -1;
+    if (pos < n_rec) {
+      ent[q] = s.idx[pos];
+      const int r = F::TAG_SLOT ? (int)s.rowof[ent[q] >> kTagShift] : ent[q] >> kTagShift;
+      const uint32_t mine = (uint32_t)s.z[ent[q] & kTagMask];
+      const int lo = s.start[r], cnt = s.cnt[r];
+      int before = 0;
+      for (int j = lo; j < lo + cnt; ++j)
+        before += (uint32_t)s.z[s.idx[j] & kTagMask] < mine ? 1 : 0;
+      at[q] = lo + before;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < PT; ++q)
+    if (at[q] >= 0) s.idx[at[q]] = ent[q];
+  __syncthreads();
+}
+
+// A bucket split by tile range (parts > 1), first half: this part leaves its sums (acc) in its scratch slot and
+// learns whether it was the last part to arrive; the last one goes on with sum_part_slots and the update, the others
+// are done with the bucket.  The arrival counter is left at 0 for a further item pass over the same partition.
+// `slots` (the bucket's slots) and `lc` (this lane's column) come back for the second half.  k, part and parts are
+// workgroup-uniform (three barriers, and s_last decides for the whole workgroup); row_t is the TRUE local row of this
+// lane group: slots are indexed by it, every part deals its own rows.
+// (Two functions and the caller's `continue` between them: one function that returned early for the other parts
+// changed the code of the loaders' binary search in the fused and unfused D = 64 item forms.)
+template <class F>
+__device__ __forceinline__ bool leave_part_sums(const OwnerArgs& a, const OwnerLds& s, int tid, int k, int part,
+                                                int parts, bool finisher, int row_t, const float4& acc, float*& slots,
+                                                int& lc) {
+  constexpr int D = F::D, R = F::R;
+  // (the base goes through an empty asm: otherwise scratch + this lane's offset is hoisted out of the bucket
+  // loop into a VGPR pair the item pass does not have — it was spilled to scratch memory)
+  float* sbase = a.scratch;
+  asm volatile("" : "+s"(sbase));
+  slots = sbase + (int64_t)split_slot(a.split, a.nb)[k] * (R * D);
+  // (the lane's column is taken afresh from the thread index here too: kept from the kernel's start for this
+  // rare path, it was the register pair the fused D = 64 form went to scratch memory for)
+  int t3 = tid;
+  asm volatile("" : "+v"(t3));
+  lc = 4 * (t3 % F::LPR);
+  if (finisher) st4(slots + (int64_t)part * (R * D) + row_t * D + lc, acc);
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) {
+    *s.last = atomicAdd(split_arrive(a.split, a.nb) + k, 1) == parts - 1;
+    // every part has arrived: the counter starts clean for a further item pass over the same partition
+    if (*s.last) split_arrive(a.split, a.nb)[k] = 0;
+  }
+  __syncthreads();
+  const bool last = *s.last != 0;
+  __syncthreads();                           // s_last may be rewritten by the next bucket
+  return last;
+}
+
+// Second half, the last part only: the sums of all parts of this lane group's row, added in part order (a fixed order:
+// the deterministic mode survives).
+template <class F>
+__device__ __forceinline__ float4 sum_part_slots(const float* slots, int lc, int parts, int row_t, bool finisher) {
+  constexpr int D = F::D, R = F::R;
+  __threadfence();
+  float4 acc = zero4();
+  if (finisher) {
+    for (int q = 0; q < parts; ++q) {
+      const float4 p = ld4(slots + (int64_t)q * (R * D) + row_t * D + lc);
+      acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w;
+    }
+  }
+  return acc;
+}
+
+template <int D, bool USER, bool FUSE_ADAM, bool DET, int RPWX = 0>
+__global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(OwnerArgs a) {
+  using F = OwnerForm<D, USER, FUSE_ADAM, DET, RPWX>;
+  constexpr int LPR = F::LPR, GPW = F::GPW, RPW = F::RPW, R = F::R, DEAL_BAR = F::DEAL_BAR, CAP = F::CAP, PT = F::PT;
+  constexpr bool DEAL = F::DEAL, TAG_SLOT = F::TAG_SLOT, LOOKUP = F::LOOKUP;
   __shared__ int s_pre[kTileGroup + 1];          // flattened start of every tile's segment
   __shared__ int s_base[kTileGroup];             // where the segment sits in the record array
   __shared__ int s_cnt[kWave];                   // records per local row in this chunk
@@ -599,6 +834,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
   const int row_l = wave * RPW + (finisher ? grp : 0);   // this lane group's slot (= its row until the bucket is bound)
   float loss = 0.0f;
   __shared__ int s_last;
+  const OwnerLds s = {s_pre, s_base, s_cnt, s_start, s_rowof, s_x, s_y, s_z, s_idx, s_scan, &s_n, &s_last};
   if (USER && (int)blockIdx.x < a.build_blocks) {
     // the user pass's first workgroups size the item buckets for the item pass that follows (no launch of its own;
     // first, so that they are done long before the owners)
@@ -618,6 +854,9 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
 
   for (int ks = helper ? (int)blockIdx.x : a.bucket_begin + (int)blockIdx.x - hb;
        helper ? ks == (int)blockIdx.x : ks < a.bucket_end; ks += owners) {
+    // ---- bucket selection: which bucket k, which part of how many, and which tiles [t_begin, t_end) this trip works
+    // on, for an owner, a tile-range helper and a row helper.  (inline: as a function with `int&` results, and with
+    // only the pool rules or only the tile range lifted, the item forms changed by 87 to 2,970 lines, some to 64 VGPRs)
     // workgroups start in slot order: the caller may put heavy buckets first (wave-uniform: kept in a scalar register)
     int k, part = 0, parts = 1;
     // rows shared out (YR_ROWSPLIT): parts = -S < 0, and this workgroup keeps the local rows r with
@@ -671,6 +910,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
     // (a row part reads every tile)
     const int t_begin = parts < 0 ? 0 : __builtin_amdgcn_readfirstlane(a.T * part / parts);
     const int t_end = parts < 0 ? a.T : __builtin_amdgcn_readfirstlane(a.T * (part + 1) / parts);
+    // ---- the row this lane group finishes, until the deal: slot = row
     int row_t = row_l;                           // the local row this lane group finishes
     int row_f = k * R + row_t;
     bool valid_f = finisher && row_f < a.rows && (USER || row_kept(row_t, part, parts));
@@ -685,109 +925,31 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
 
     for (int tg0 = t_begin; tg0 < t_end; tg0 += kTileGroup) {
       const int nt = min(kTileGroup, t_end - tg0);
-      // segment descriptors of bucket k in tiles [tg0, tg0 + nt), exclusive scan of their lengths
-      int len = 0;
-      if (tid < nt) {
-        const int32_t* orow = a.off + (int64_t)(tg0 + tid) * (a.nb + 1) + k;
-        const int o0 = orow[0], o1 = orow[1];
-        len = o1 - o0;
-        s_base[tid] = (tg0 + tid) * a.tile_stride + o0;
-      }
-      int inc = 0, before = 0;
-      if (nt > kWave) {
-        inc = wave_inclusive_scan(len, lane);
-        if (lane == kWave - 1) s_scan[wave] = inc;
-        __syncthreads();
-        for (int w = 0; w < wave; ++w) before += s_scan[w];
-      } else if (wave == 0) {                    // up to 64 tiles: one wave scans
-        inc = wave_inclusive_scan(len, lane);
-      }
-      if (nt > kWave || wave == 0) {
-        s_pre[tid] = before + inc - len;
-        if (lane == kWave - 1) s_pre[tid + 1] = before + inc;   // entry after a wave's last (the total after the last wave)
-      }
-      __syncthreads();
-      const int total = s_pre[nt];
+      const int total = scan_segments(a, s, tid, k, tg0, nt);
       YR_STAMP(2);
 
       for (int c0 = 0, cend = 0, sub = 0; c0 < total; c0 = cend) {
         cend = min(total, c0 + CAP);
-        // DET: which records share a chunk must not depend on the (arbitrary) order inside a tile's segment.  Chunks
-        // are cut at tile boundaries; a segment larger than a chunk is taken in WINDOWS of triplet ids (a window of
-        // CAP ids holds at most CAP user-side records, one of CAP / 2 ids at most CAP item occurrences): every window
-        // scans the whole segment and keeps what falls into it — a fixed set, ranked by triplet id below.
         int wt = 0;
         bool windowed = false;
-        if (DET) {
-          int tlo = 0, thi = nt;
-          while (thi - tlo > 1) {                    // the tile whose segment starts at c0 (chunks start at boundaries)
-            const int mid = (tlo + thi) >> 1;
-            if (s_pre[mid] <= c0) tlo = mid; else thi = mid;
-          }
-          wt = tlo;
-          windowed = s_pre[wt + 1] - s_pre[wt] > CAP;
-          if (!windowed && cend < total) {
-            tlo = 0, thi = nt;
-            while (thi - tlo > 1) {
-              const int mid = (tlo + thi) >> 1;
-              if (s_pre[mid] <= cend) tlo = mid; else thi = mid;
-            }
-            if (s_pre[tlo] > c0) cend = s_pre[tlo];
-          }
-        }
+        if (DET) windowed = cut_chunk_at_tiles<CAP>(s_pre, nt, c0, total, cend, wt);
         if (tid < kWave) s_cnt[tid] = 0;
         if (DET && tid == 0) s_n = 0;
         __syncthreads();
-        // load this chunk's records (flattened index -> tile by binary search) into LDS in load
-        // order and rank them by local row; key = local row | rank << 8
+        // ---- loaders: this chunk's records into s_x / s_y (/ s_z) in load order, ranked by local row (s_cnt);
+        // key = local row | rank << 8, -1 for none
         int key[PT];
         int n_rec = cend - c0;
         if (DET && windowed) {
-          constexpr int W = USER ? CAP : CAP / 2;
-          const int tile_ids = USER ? a.tile_stride : a.tile_stride >> 1;
-          const int seg = s_pre[wt + 1] - s_pre[wt];
-          const uint32_t rbase = (uint32_t)s_base[wt];
-          const uint32_t id_lo = (uint32_t)(tg0 + wt) * (uint32_t)tile_ids + (uint32_t)sub * (uint32_t)W;
-          for (int sidx = tid; sidx < seg; sidx += kBlock) {
-            if (USER) {
-              const int4 r = static_cast<const int4*>(a.recs)[rbase + sidx];
-              if ((uint32_t)r.z - id_lo < (uint32_t)W) {
-                const int slot = atomicAdd(&s_n, 1);
-                s_x[slot] = r.x; s_y[slot] = r.y; s_z[slot] = r.z;
-                s_idx[slot] = (unsigned short)r.w;     // the local row, until the keys below are taken
-              }
-            } else {
-              const int2 oc = static_cast<const int2*>(a.recs)[rbase + sidx];
-              const uint32_t b = (uint32_t)(oc.y & 0x7fffffff);
-              if (b - id_lo < (uint32_t)W && row_kept((int)((uint32_t)oc.x >> kOccShift), part, parts)) {
-                const float g = a.coeff[b];
-                const int slot = atomicAdd(&s_n, 1);
-                s_x[slot] = oc.x & kOccMask;
-                s_y[slot] = __float_as_int(oc.y < 0 ? -g : g);
-                s_z[slot] = oc.y;
-                s_idx[slot] = (unsigned short)((uint32_t)oc.x >> kOccShift);
-              }
-            }
-          }
-          __syncthreads();
-          n_rec = s_n;
-#pragma unroll
-          for (int q = 0; q < PT; ++q) {
-            const int c = tid + q * kBlock;
-            key[q] = -1;
-            if (c < n_rec) {
-              const int local = s_idx[c];
-              key[q] = local | (atomicAdd(&s_cnt[local], 1) << 8);
-            }
-          }
-          ++sub;                                       // the next window of this segment, or the next tile boundary
-          if (sub * W >= tile_ids) { sub = 0; cend = s_pre[wt + 1]; }
-          else cend = c0;
+          n_rec = load_window<F>(a, s, tid, part, parts, tg0, wt, c0, sub, cend, key);
           if (n_rec == 0) {                            // workgroup-uniform: nothing in this window
             __syncthreads();
             continue;
           }
         } else {
+        // plain loader: record c0 + tid + q kBlock of the flattened stream (index -> tile by the search of tile_of,
+        // address from s_base) goes to position tid + q kBlock.  (inline: as a function, whole or per role, with
+        // the keys by reference or by value, 42 to 94 lines of the D = 64 forms changed; so did tile_of alone here)
         uint32_t addr[PT];
 #pragma unroll
         for (int q = 0; q < PT; ++q) {
@@ -841,7 +1003,10 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
         }
         }
         __syncthreads();
-        // sorted stream = light rows in row order, then the heavy rows (more than heavy_t records)
+        // ---- stream layout: sorted stream = light rows in slot order, then the heavy rows (more than heavy_t records).
+        // Wave 0 binds rows to slots (once per bucket: s_slotof, s_rowof) and scans the counts into s_light, s_start
+        // (s_n: records in the stream); after a barrier every thread puts its records into s_idx.  (inline: as one
+        // function or as its two halves, 9 to 122 lines of the D = 64 forms changed)
         if (wave == 0) {
           if (DEAL && !bound) {
             // the deal is R serial steps of wave 0 (about 1.4 us at R = 16) while the other waves wait, and a walk
@@ -887,42 +1052,18 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
             s_idx[s_start[row] + (key[q] >> 8)] = (unsigned short)((tid + q * kBlock) | (tag << kTagShift));
           }
         __syncthreads();
-        if (DET) {
-          // the ranks above came from LDS atomics in arrival order: re-rank every row by triplet id
-          // (unique inside a row), so that the order of every floating-point sum below is fixed
-          int at[PT];
-          unsigned short ent[PT];
-#pragma unroll
-          for (int q = 0; q < PT; ++q) {
-            const int pos = tid + q * kBlock;
-            at[q] = -1;
-            if (pos < n_rec) {
-              ent[q] = s_idx[pos];
-              const int r = TAG_SLOT ? (int)s_rowof[ent[q] >> kTagShift] : ent[q] >> kTagShift;
-              const uint32_t mine = (uint32_t)s_z[ent[q] & ((1 << kTagShift) - 1)];
-              const int lo = s_start[r], cnt = s_cnt[r];
-              int before = 0;
-              for (int j = lo; j < lo + cnt; ++j)
-                before += (uint32_t)s_z[s_idx[j] & ((1 << kTagShift) - 1)] < mine ? 1 : 0;
-              at[q] = lo + before;
-            }
-          }
-          __syncthreads();
-#pragma unroll
-          for (int q = 0; q < PT; ++q)
-            if (at[q] >= 0) s_idx[at[q]] = ent[q];
-          __syncthreads();
-        }
-        // light rows: wave w walks the records of ITS slots [w RPW, (w+1) RPW), one per lane group and step
+        if (DET) rerank_by_id<F>(s, tid, n_rec);
+        // ---- light rows: wave w walks the records of ITS slots [w RPW, (w+1) RPW), one per lane group and step
         {
           float4 cur = zero4();
           walk_stream<D, USER, false, LOOKUP>(a, s_idx, s_x, s_y, s_z, s_own, s_slotof, s_light[wave * RPW],
                                             s_light[wave * RPW + RPW], grp, GPW, wave * RPW, grp, l, sums, cur, loss);
 #ifdef YR_STAMPS
-          if (first_bucket) walk_iters += (s_light[wave * RPW + RPW] - s_light[wave * RPW] + GPW * (USER ? kUserUnroll : kItemUnroll) - 1) / (GPW * (USER ? kUserUnroll : kItemUnroll));
+          if (first_bucket) walk_iters += walk_steps<USER>(s_light[wave * RPW + RPW] - s_light[wave * RPW], GPW);
 #endif
         }
-        // heavy rows of the chunk: all waves on one row, partial sums combined in wave order
+        // ---- heavy rows of the chunk: all waves on one row, partial sums combined in wave order (s_heavy).  (inline: as
+        // a function, the loop or one row of it, 15 to 32 lines of the D = 64 user forms changed)
         if (n_rec - s_light[kWave] > 0) {   // workgroup-uniform
 #pragma unroll 1
           for (int r = 0; r < R; ++r) {
@@ -933,7 +1074,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
             walk_stream<D, USER, true, LOOKUP>(a, s_idx, s_x, s_y, s_z, s_own, s_slotof, lo, lo + cnt, wave * GPW + grp,
                                              kWavesPerBlock * GPW, 0, grp, l, sums, t, loss);
 #ifdef YR_STAMPS
-            if (first_bucket) { walk_iters += (cnt + kWavesPerBlock * GPW * (USER ? kUserUnroll : kItemUnroll) - 1) / (kWavesPerBlock * GPW * (USER ? kUserUnroll : kItemUnroll)); heavy_iters += 1; }
+            if (first_bucket) { walk_iters += walk_steps<USER>(cnt, kWavesPerBlock * GPW); heavy_iters += 1; }
 #endif
             cross_group_sum<LPR>(t);
             if (grp == 0) s_heavy[wave][l] = t;
@@ -954,6 +1095,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
 
     YR_STAMP(3);
     float4 acc = sums.finish(grp);
+    // ---- final row binding.  (inline: with reference results or a struct returned, 18 to 845 lines of the D = 64 forms changed)
     if (DEAL) {                                  // the row this slot was dealt (a bucket without records: the identity)
       if (bound) row_t = s_rowof[row_l];
       row_f = k * R + row_t;
@@ -964,41 +1106,15 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
       asm volatile("" : "+v"(t2));
       o_f = (uint32_t)(row_f * D + 4 * (t2 % LPR));
     }
+    // ---- cross-part combine: a bucket split by tile range; the last part to arrive goes on with the sum of all parts
     if (!USER && parts > 1) {
-      // a split bucket: leave this part's sums in its scratch slot; the last part to arrive adds the slots in part
-      // order and goes on to the update, the others are done with the bucket
-      // (the base goes through an empty asm: otherwise scratch + this lane's offset is hoisted out of the bucket
-      // loop into a VGPR pair the item pass does not have — it was spilled to scratch memory)
-      float* sbase = a.scratch;
-      asm volatile("" : "+s"(sbase));
-      float* slots = sbase + (int64_t)split_slot(a.split, a.nb)[k] * (R * D);
-      // slots are indexed by the TRUE local row: every part deals its own rows
-      // (the lane's column is taken afresh from the thread index here too: kept from the kernel's start for this
-      // rare path, it was the register pair the fused D = 64 form went to scratch memory for)
-      int t3 = tid;
-      asm volatile("" : "+v"(t3));
-      const int lc = 4 * (t3 % LPR);
-      if (finisher) st4(slots + (int64_t)part * (R * D) + row_t * D + lc, acc);
-      __threadfence();
-      __syncthreads();
-      if (tid == 0) {
-        s_last = atomicAdd(split_arrive(a.split, a.nb) + k, 1) == parts - 1;
-        // every part has arrived: the counter starts clean for a further item pass over the same partition
-        if (s_last) split_arrive(a.split, a.nb)[k] = 0;
-      }
-      __syncthreads();
-      const bool last = s_last != 0;
-      __syncthreads();                           // s_last may be rewritten by the next bucket
-      if (!last) continue;
-      __threadfence();
-      acc = zero4();
-      if (finisher) {
-        for (int q = 0; q < parts; ++q) {
-          const float4 t = ld4(slots + (int64_t)q * (R * D) + row_t * D + lc);
-          acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
-        }
-      }
+      float* slots;
+      int lc;
+      if (!leave_part_sums<F>(a, s, tid, k, part, parts, finisher, row_t, acc, slots, lc)) continue;
+      acc = sum_part_slots<F>(slots, lc, parts, row_t, finisher);
     }
+    // ---- row update: fused Adam, or the dense gradient row.  (inline: as a function, whole or the four adam_element
+    // calls alone, 14 to 1,441 lines of the D = 64 forms changed: the kernel-argument loads move)
     if (valid_f) {
       if (FUSE_ADAM) {
         float4 own = USER ? s_own[row_t * LPR + l] : ld4o(a.own_old, o_f);
@@ -1035,6 +1151,8 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
     if ((int)blockIdx.x == hb)                    // slots no workgroup owns
       for (int i = owners + tid; i < YR_LOSS_PARTIALS; i += kBlock) a.loss_partials[i] = 0.0f;
   } else if (a.finalize && (int)blockIdx.x == hb) {
+    // ---- loss reduction, as pull_loss_finalize_kernel.  (inline, twice: one function for both, in four shapes,
+    // reordered four instructions of the D = 64 item forms)
     // the user pass (previous launch) left one partial per workgroup: fixed-order sum -> step loss
     float s = 0.0f;
     for (int i = tid; i < YR_LOSS_PARTIALS; i += kBlock) s += a.loss_partials[i];
@@ -1227,7 +1345,7 @@ static int pull_apply_impl(const float* U_old, float* U_new, float* I, float* mU
     ua.bucket_begin = 0; ua.bucket_end = p.nbU;
     ua.order = nullptr;
     ua.heavy_t = kHeavyRow; ua.inv_batch = inv_batch; ua.adam = adam;
-    // the last kSplitBuilders workgroups size the item buckets (oversize ones are shared out in the item pass)
+    // the first build_blocks workgroups size the item buckets (oversize ones are shared out in the item pass)
     ua.build_blocks = (p.nbI * kBuildLanes + kBlock - 1) / kBlock;
     ua.b_off = (const int32_t*)(w + p.o_offI); ua.b_nb = p.nbI;
     const SplitRule rule = split_rule(B, p.nbI, D);
