@@ -36,10 +36,12 @@ def _feistel(x, half_bits, k0, k1):
     return (L << hb) | R
 
 
-def _philox4x32_7(c0, c1, c2, c3, k0, k1):
+def philox4x32(c0, c1, c2, c3, k0, k1, rounds):
+    """Philox4x32 with ``rounds`` rounds (csrc/philox.h): 10 is the standard generator (dropout masks), 7 the
+    sampler's.  Counter words as arrays (or scalars), key words scalars; returns four uint64 arrays below 2^32."""
     c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) for c in (c0, c1, c2, c3))
     k0, k1 = np.uint64(k0), np.uint64(k1)
-    for _ in range(7):
+    for _ in range(rounds):
         p0 = np.uint64(0xD2511F53) * c0
         p1 = np.uint64(0xCD9E8D57) * c2
         hi0, lo0, hi1, lo1 = p0 >> np.uint64(32), p0 & U32, p1 >> np.uint64(32), p1 & U32
@@ -47,6 +49,10 @@ def _philox4x32_7(c0, c1, c2, c3, k0, k1):
         k0 = (k0 + np.uint64(0x9E3779B9)) & U32
         k1 = (k1 + np.uint64(0xBB67AE85)) & U32
     return c0, c1, c2, c3
+
+
+def _philox4x32_7(c0, c1, c2, c3, k0, k1):
+    return philox4x32(c0, c1, c2, c3, k0, k1, 7)
 
 
 def half_bits_for(n_rows):
