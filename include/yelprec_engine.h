@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YR_ENGINE_VERSION 32
+#define YR_ENGINE_VERSION 33
 
 #define YR_ERR_UNSUPPORTED (-1) /* embedding width / option not compiled in   */
 #define YR_ERR_BADARG      (-2) /* null pointer, negative size, misalignment  */
@@ -825,6 +825,58 @@ int yr_s3rec_seq_scores(const float *item_emb, const float *h, const int64_t *po
 int yr_s3rec_candidate_scores(const float *item_emb, const float *h_last, const int64_t *pos_item,
                               const int64_t *neg_items, int64_t B, int64_t C, int E, int64_t num_items,
                               float *pos_pred, float *neg_preds, int32_t *err_flag, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * S3Rec training              (reference models/s3rec.py:53-100,184-214 in train() mode and its autograd;
+ *   trainers/s3rec_trainer.py:233-247 drives it through finetune + BPRLoss + backward)
+ * Shapes, packed `params` and limits as for yr_s3rec_encode.  `workspace` (caller-owned, 16-byte aligned) holds
+ * yr_s3rec_train_workspace_floats(B, L, E, heads, blocks) floats (a negative YR_ERR_* for refused sizes): block
+ * after block, with R = B L rows of index b L + i, every array [R][width] row-major and usable as a GEMM operand,
+ *   stash (written by the forward):   h_in E | qkv 3 heads E (Q[heads] | K[heads] | V[heads], K masked) | A heads E |
+ *     x1 E | xh1 E | relu E | xh2 E | rstd 4        (xh: the LayerNorm's normalised value; rstd1, rstd2, two unused)
+ *   deltas (written by the backward): g2 E | gx2 E | d2m E | dz1 E | g1 E | gx1 E | d1m E | dqkv 3 heads E | dA heads E
+ *   = (12 + 8 heads) E + 4 floats per row and block.  P is recomputed from the stashed Q and K.
+ * Dropout (s3rec.py:62,68: on the attention output after W_o, b_o and on the FFN output after W_2, b_2, before the
+ * residual): a pure function of (seed, site = 2 block + {0, 1}, flat index in [B, L, E]) in the law of
+ * yr_dropout_seeded — float4 group q draws Philox4x32-10 at the counter (q lo, q hi, site, 0), word t belongs to
+ * element 4 q + t, kept where u01 >= p, scaled by 1 / (1 - p).  0 <= p < 1; the backward draws the mask again.
+ * yr_s3rec_encode_train: out [B][L][E] as yr_s3rec_encode (bit for bit at p = 0) and the stash
+ *   (_embedding_layer + _self_attention_block in train() mode, s3rec.py:96-97).
+ * yr_s3rec_backward: from dh_out [B][L][E] the deltas of every block and d_emb [B][L][E], the gradient of
+ *   item_emb[X] + pos_enc (what autograd runs for s3rec.py:56-71,196-214), one workgroup per sequence:
+ *     d_s2 = LayerNorm2 backward of g2;  dz1 = (d_s2 mask2 W_2) * (relu > 0);  g1 = dz1 W_1;  d_s1 = LayerNorm1
+ *     backward of g1;  dA = (d_s1 mask1) W_o;  per head dV = P^T dA_h, dP = dA_h V^T (keys j <= i), dS = P (dP -
+ *     rowsum(dP P)) / sqrt(E), dQ = dS K, dK = (dS^T Q) * pad[j];  dh_in = d_s2 + d_s1 + dqkv (W_q | W_k | W_v)
+ *     (both residuals add the block's input: s3rec.py:64,70).
+ *   The parameter gradients are products and column sums over the R rows that the caller runs (yr_gemm_f32 with
+ *   transA = 1, yr_colsum), into the packed layout:  d(W_q | W_k | W_v) = dqkv^T h_in;  dW_o = d1m^T A,
+ *   db_o = colsum(d1m);  d ln1.weight = colsum(gx1), d ln1.bias = colsum(g1);  dW_1 = dz1^T x1, db_1 = colsum(dz1);
+ *   dW_2 = d2m^T relu, db_2 = colsum(d2m);  d ln2.weight = colsum(gx2), d ln2.bias = colsum(g2);
+ *   d pos_enc = colsum of d_emb viewed [B][L E].
+ * yr_s3rec_score_grad: dh_out[r] = dpos_preds[r] item_emb[pos_items[r]] + dneg_preds[r] item_emb[neg_items[r]]
+ *   (backward of _sequence_prediction_layer w.r.t. the encoder output, s3rec.py:98-99).
+ * yr_s3rec_item_grad: d_item [num_items + 1][E] += d_emb rows scattered by X, dpos_preds[r] h[r] by pos_items and
+ *   dneg_preds[r] h[r] by neg_items (embedding_dense_backward of the three item_embedding lookups; X = 0 is an
+ *   ordinary row).  The rows repeat within a step, so the caller hands the 3 rows lookups X | pos_items | neg_items
+ *   sorted by id: sorted_ids [3 rows] ascending and order [3 rows] (order[k] = s rows + r: lookup r of list s; a
+ *   stable sort makes the result a function of the batch alone).  Two launches, fixed summation order, no atomics:
+ *   running sums per run of equal ids inside chunks of 256 sorted lookups into partial [3 rows][E] (scratch, any
+ *   contents), then per item the partials of its chunks, first to last.
+ * An id outside [0, num_items] raises YR_FLAG_BAD_ITEM and contributes nothing.
+ * ------------------------------------------------------------------------- */
+int64_t yr_s3rec_train_workspace_floats(int64_t B, int L, int E, int heads, int blocks);
+int yr_s3rec_encode_train(const float *item_emb, const float *pos_enc, const float *params, const int64_t *X,
+                          int64_t B, int L, int E, int heads, int blocks, int64_t num_items, uint64_t seed, double p,
+                          float *out, float *workspace, int64_t workspace_floats, int32_t *err_flag, void *stream);
+int yr_s3rec_backward(const float *params, const int64_t *X, const float *dh_out, int64_t B, int L, int E, int heads,
+                      int blocks, uint64_t seed, double p, float *workspace, int64_t workspace_floats, float *d_emb,
+                      void *stream);
+int yr_s3rec_score_grad(const float *item_emb, const int64_t *pos_items, const int64_t *neg_items,
+                        const float *dpos_preds, const float *dneg_preds, int64_t rows, int E, int64_t num_items,
+                        float *dh_out, int32_t *err_flag, void *stream);
+int yr_s3rec_item_grad(const int64_t *sorted_ids, const int64_t *order, const float *d_emb, const float *h,
+                       const float *dpos_preds, const float *dneg_preds, int64_t rows, int E, int64_t num_items,
+                       float *partial, float *d_item, int32_t *err_flag, void *stream);
 
 #ifdef __cplusplus
 }

@@ -60,6 +60,13 @@ BUDGETS = [
      "a workgroup per sequence, LDS-bound: one to two workgroups of four waves per CU at the reference's shapes "
      "(81.5 KB at E = 64, L = 50), so two waves per SIMD (512 / 2 -> 256) is all the registers have to allow"),
     (r"yr::s3rec_scores_kernel", 64, 0, "16 lanes per dot product, streaming: eight waves per SIMD"),
+    (r"void yr::s3rec_encode_train_kernel<(16|32|64|128)>", 256, 1024,
+     "S3Rec training forward: a workgroup per sequence and LDS-bound like the scoring encoder, two waves per SIMD"),
+    (r"void yr::s3rec_backward_kernel<(16|32|64|128)>", 512, 1024,
+     "S3Rec backward: the same tiles plus one row of floats; at the reference's shape (81.7 KB at E = 64, L = 50) LDS "
+     "admits one workgroup per CU, so one wave per SIMD (512 registers) costs nothing there; no scratch"),
+    (r"yr::s3rec_(score_grad|item_partials|item_combine)_kernel", 64, 0,
+     "element-wise pass and the two ordered passes of the item gradient: eight waves per SIMD"),
 ]
 # Scratch (spilled registers) per lane.  The forms the benchmark and the trainers run by default — width 64, summation
 # order free — must have none; the deterministic-order forms and some forms of the other widths are held at 64 VGPRs by

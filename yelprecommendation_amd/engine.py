@@ -1334,3 +1334,205 @@ def s3rec_candidate_scores(item_emb, h_last, pos_item, neg_items, out=None, err_
                                         _dev(pos, f32, "pos_pred"), _dev(neg, f32, "neg_preds"),
                                         _opt(err_flag, torch.int32, "flag"), _stream()), "yr_s3rec_candidate_scores")
     return pos, neg
+
+
+# ---- S3Rec training (csrc/s3rec.hip: the stash-keeping forward, the backward, the item gradient) ----
+_S3REC_WS_ARRAYS = (("h_in", 1, 0), ("qkv", 0, 3), ("A", 0, 1), ("x1", 1, 0), ("xh1", 1, 0), ("relu", 1, 0),
+                    ("xh2", 1, 0), ("rstd", None, None), ("g2", 1, 0), ("gx2", 1, 0), ("d2m", 1, 0), ("dz1", 1, 0),
+                    ("g1", 1, 0), ("gx1", 1, 0), ("d1m", 1, 0), ("dqkv", 0, 3), ("dA", 0, 1))
+
+
+def s3rec_train_workspace_floats(B, L, E, heads, blocks):
+    """Floats of the training workspace (yr_s3rec_train_workspace_floats)."""
+    n = _lib.load().yr_s3rec_train_workspace_floats(B, L, E, heads, blocks)
+    if n < 0:
+        check(int(n), "yr_s3rec_train_workspace_floats")
+    return int(n)
+
+
+def s3rec_workspace_views(ws, B, L, E, heads, blocks):
+    """[{name: [B L, width] view}] per block of the training workspace (layout: include/yelprec_engine.h)."""
+    R, at, out = B * L, 0, []
+    for _ in range(blocks):
+        views = {}
+        for name, e, he in _S3REC_WS_ARRAYS:
+            width = 4 if e is None else (e + he * heads) * E
+            views[name] = ws[at:at + R * width].view(R, width)
+            at += R * width
+        out.append(views)
+    if at != ws.numel():
+        raise EngineError(f"s3rec workspace: {ws.numel()} floats, the layout takes {at}")
+    return out
+
+
+def _s3rec_train_dims(params, X, E, heads, blocks, ws, what):
+    if X.dim() != 2:
+        raise EngineError(f"{what}: X [B, L] expected, got {tuple(X.shape)}")
+    if params.numel() != blocks * s3rec_block_floats(E, heads):
+        raise EngineError(f"{what}: packed parameters hold {params.numel()} floats, "
+                          f"{blocks * s3rec_block_floats(E, heads)} expected")
+    if ws.dim() != 1:
+        raise EngineError(f"{what}: the workspace is a flat f32 buffer")
+    return X.shape
+
+
+def s3rec_encode_train(item_emb, pos_enc, params, X, heads, blocks, seed=0, p=0.0, workspace=None, out=None,
+                       err_flag=None):
+    """(h [B, L, E], workspace): yr_s3rec_encode_train — the encoder in train() mode (dropout ``p`` from ``seed``)
+    keeping what s3rec_backward consumes in ``workspace`` (allocated when None)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    if item_emb.dim() != 2 or X.dim() != 2 or pos_enc.shape != (X.shape[1], item_emb.shape[1]):
+        raise EngineError(f"s3rec_encode_train: X [B, L], item_emb [num_items + 1, E], pos_enc [L, E] expected, got "
+                          f"{tuple(X.shape)} / {tuple(item_emb.shape)} / {tuple(pos_enc.shape)}")
+    E = item_emb.shape[1]
+    if workspace is None:
+        workspace = torch.empty(s3rec_train_workspace_floats(X.shape[0], X.shape[1], E, heads, blocks), dtype=f32,
+                                device=X.device)
+    B, L = _s3rec_train_dims(params, X, E, heads, blocks, workspace, "s3rec_encode_train")
+    if out is None:
+        out = torch.empty((B, L, E), dtype=f32, device=X.device)
+    elif tuple(out.shape) != (B, L, E):
+        raise EngineError(f"s3rec_encode_train: out {tuple(out.shape)}, expected {(B, L, E)}")
+    check(lib.yr_s3rec_encode_train(_dev(item_emb, f32, "item_emb"), _dev(pos_enc, f32, "pos_enc"),
+                                    _dev(params, f32, "params"), _dev(X, torch.int64, "X"), B, L, E, heads, blocks,
+                                    item_emb.shape[0] - 1, int(seed) & 0xFFFFFFFFFFFFFFFF, float(p), _dev(out, f32, "out"),
+                                    _dev(workspace, f32, "workspace"), workspace.numel(),
+                                    _opt(err_flag, torch.int32, "flag"), _stream()), "yr_s3rec_encode_train")
+    return out, workspace
+
+
+def s3rec_backward(params, X, dh_out, workspace, heads, blocks, seed=0, p=0.0, d_emb=None):
+    """d_emb [B, L, E] from dh_out [B, L, E]; the deltas of every block go to ``workspace`` (yr_s3rec_backward)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    E = dh_out.shape[-1]
+    B, L = _s3rec_train_dims(params, X, E, heads, blocks, workspace, "s3rec_backward")
+    if tuple(dh_out.shape) != (B, L, E):
+        raise EngineError(f"s3rec_backward: dh_out {tuple(dh_out.shape)}, expected {(B, L, E)}")
+    if d_emb is None:
+        d_emb = torch.empty((B, L, E), dtype=f32, device=X.device)
+    elif tuple(d_emb.shape) != (B, L, E):
+        raise EngineError(f"s3rec_backward: d_emb {tuple(d_emb.shape)}, expected {(B, L, E)}")
+    check(lib.yr_s3rec_backward(_dev(params, f32, "params"), _dev(X, torch.int64, "X"), _dev(dh_out, f32, "dh_out"),
+                                B, L, E, heads, blocks, int(seed) & 0xFFFFFFFFFFFFFFFF, float(p),
+                                _dev(workspace, f32, "workspace"), workspace.numel(), _dev(d_emb, f32, "d_emb"),
+                                _stream()), "yr_s3rec_backward")
+    return d_emb
+
+
+S3REC_GRAD_CHUNK_ROWS = 2048
+
+
+_s3rec_side_streams = {}
+
+
+def _s3rec_rows_products(jobs):
+    """out [M, N] = D^T Xm over the rows for every (D, Xm, out) of ``jobs``, summed on two levels: a product per
+    S3REC_GRAD_CHUNK_ROWS rows, then a column sum over the partial products — no atomics, and the f32 rounding of a
+    sum over B L rows stays that of a sum over a chunk (one accumulator chain over 12,850 rows measured 1.7 x the
+    tests' bar).  A chunk's product fills a handful of workgroups (one per 64 x 64 output tile), so the
+    chunk products of a large batch are dealt to four streams that rejoin before the column sums."""
+    chunk = S3REC_GRAD_CHUNK_ROWS
+    small, chunked = [], []
+    for D, Xm, out in jobs:
+        if D.shape[0] <= chunk:
+            small.append((D, Xm, out))
+        else:
+            parts = torch.empty(((D.shape[0] + chunk - 1) // chunk, out.numel()), dtype=torch.float32, device=D.device)
+            chunked.append((parts, out))
+            small.extend((D[c * chunk:(c + 1) * chunk], Xm[c * chunk:(c + 1) * chunk], parts[c].view(out.shape))
+                         for c in range(parts.shape[0]))
+    if len(small) < 16:
+        for D, Xm, out in small:
+            gemm_f32(D, Xm, transA=True, out=out)
+    else:
+        cur = torch.cuda.current_stream()
+        side = _s3rec_side_streams.setdefault(cur.device, [torch.cuda.Stream(cur.device) for _ in range(3)])
+        for st in side:
+            st.wait_stream(cur)
+        for k, (D, Xm, out) in enumerate(small):
+            with torch.cuda.stream(cur if k % 4 == 0 else side[k % 4 - 1]):
+                gemm_f32(D, Xm, transA=True, out=out)
+        for st in side:
+            cur.wait_stream(st)
+    for parts, out in chunked:
+        colsum(parts, out=out.view(-1))
+
+
+def _s3rec_rows_sum(D, B, L, out):
+    """out [width] = the column sums of D [B L, width], summed on two levels: over the sequences, then over the
+    positions (the order d positional_encoding takes)."""
+    colsum(colsum(D.view(B, L * D.shape[1])).view(L, D.shape[1]), out=out)
+    return out
+
+
+def s3rec_param_grads(workspace, B, L, E, heads, blocks, out=None):
+    """The gradient of the packed parameter buffer from the stash and the deltas of a backward pass: per block four
+    transposed products over the B L rows (yr_gemm_f32, no atomics: _s3rec_rows_products) and seven column sums
+    (yr_colsum), each ending in its place of the packed layout."""
+    n = s3rec_block_floats(E, heads)
+    if out is None:
+        out = torch.empty(blocks * n, dtype=torch.float32, device=workspace.device)
+    EE, HE = E * E, heads * E
+    jobs = []
+    for blk, v in enumerate(s3rec_workspace_views(workspace, B, L, E, heads, blocks)):
+        g = out[blk * n:(blk + 1) * n]
+        at = 0
+
+        def take(rows, cols):
+            nonlocal at
+            t = g[at:at + rows * cols]
+            at += rows * cols
+            return t.view(rows, cols) if rows > 1 else t
+
+        jobs.append((v["dqkv"], v["h_in"], take(3 * HE, E)))
+        jobs.append((v["d1m"], v["A"], take(E, HE)))
+        _s3rec_rows_sum(v["d1m"], B, L, take(1, E))
+        _s3rec_rows_sum(v["gx1"], B, L, take(1, E))
+        _s3rec_rows_sum(v["g1"], B, L, take(1, E))
+        jobs.append((v["dz1"], v["x1"], take(E, E)))
+        _s3rec_rows_sum(v["dz1"], B, L, take(1, E))
+        jobs.append((v["d2m"], v["relu"], take(E, E)))
+        _s3rec_rows_sum(v["d2m"], B, L, take(1, E))
+        _s3rec_rows_sum(v["gx2"], B, L, take(1, E))
+        _s3rec_rows_sum(v["g2"], B, L, take(1, E))
+        assert at == n == (4 * heads + 2) * EE + 7 * E
+    _s3rec_rows_products(jobs)
+    return out
+
+
+def s3rec_score_grad(item_emb, pos_items, neg_items, dpos, dneg, err_flag=None):
+    """dh_out [rows, E] = dpos[r] item_emb[pos_items[r]] + dneg[r] item_emb[neg_items[r]] (yr_s3rec_score_grad)."""
+    lib = _lib.load()
+    f32 = torch.float32
+    rows, E = dpos.numel(), item_emb.shape[1]
+    if pos_items.numel() != rows or neg_items.numel() != rows or dneg.numel() != rows:
+        raise EngineError("s3rec_score_grad: one positive, one negative and two score gradients per position expected")
+    out = torch.empty((rows, E), dtype=f32, device=item_emb.device)
+    check(lib.yr_s3rec_score_grad(_dev(item_emb, f32, "item_emb"), _dev(pos_items, torch.int64, "pos_items"),
+                                  _dev(neg_items, torch.int64, "neg_items"), _dev(dpos, f32, "dpos"),
+                                  _dev(dneg, f32, "dneg"), rows, E, item_emb.shape[0] - 1, out.data_ptr(),
+                                  _opt(err_flag, torch.int32, "flag"), _stream()), "yr_s3rec_score_grad")
+    return out
+
+
+def s3rec_item_grad(X, pos_items, neg_items, d_emb, h, dpos, dneg, d_item, err_flag=None):
+    """d_item [num_items + 1, E] += the three item_embedding lookups' gradients (yr_s3rec_item_grad): the lookups are
+    sorted by id here (a stable sort: index preparation), the sums run in the kernels in a fixed order."""
+    lib = _lib.load()
+    f32 = torch.float32
+    rows, E = dpos.numel(), d_item.shape[1]
+    if any(t.numel() != rows for t in (X, pos_items, neg_items, dneg)) or d_emb.numel() != rows * E \
+            or h.numel() != rows * E:
+        raise EngineError("s3rec_item_grad: X, pos_items, neg_items, dpos, dneg of B L entries and d_emb, h [B, L, E] expected")
+    for t, name in ((X, "X"), (pos_items, "pos_items"), (neg_items, "neg_items")):
+        _dev(t, torch.int64, name)
+    sorted_ids, order = torch.sort(torch.cat([X.reshape(-1), pos_items.reshape(-1), neg_items.reshape(-1)]), stable=True)
+    partial = torch.empty((3 * rows, E), dtype=f32, device=d_item.device)
+    check(lib.yr_s3rec_item_grad(_dev(sorted_ids, torch.int64, "sorted_ids"), _dev(order, torch.int64, "order"),
+                                 _dev(d_emb, f32, "d_emb"), _dev(h, f32, "h"), _dev(dpos, f32, "dpos"),
+                                 _dev(dneg, f32, "dneg"), rows, E, d_item.shape[0] - 1, partial.data_ptr(),
+                                 _dev(d_item, f32, "d_item"), _opt(err_flag, torch.int32, "flag"), _stream()),
+          "yr_s3rec_item_grad")
+    return d_item

@@ -9,10 +9,20 @@ Build on the CPU under the seed, then move to the GPU (as models/mf.py).
 
 ``finetune(X, pos_items, neg_items)`` and ``evaluate(X, pos_item, neg_items)`` return the reference's shapes and run
 the fused encoder of csrc/s3rec.hip (one launch from the embedding gather to the last LayerNorm) plus one score
-launch.  They are forward-only: in ``eval()`` mode under ``torch.no_grad()``.  Training (the backward pass and
-dropout) is not built yet and raises NotImplementedError, as do ``pretrain`` / ``encode`` — the reference's own
-``encode`` calls ``_self_attention_block`` without its two mask arguments (models/s3rec.py:117-118), so its
-pre-training cannot run as published and there is nothing to be faithful to.
+launch.  ``evaluate`` is forward-only: ``eval()`` mode under ``torch.no_grad()``.
+
+``finetune`` in ``train()`` mode with grad enabled trains: its two outputs carry an autograd node whose backward runs the HIP backward
+pass (csrc/s3rec.hip) and gives ``item_embedding.weight``, ``positional_encoding`` and every attention / FFN /
+LayerNorm tensor its gradient; ``attribute_embedding`` and the four ``*_weight`` take no part and keep ``grad =
+None``, as after the reference's ``backward``.  With ``dropout_ratio > 0`` it applies the reference's two dropouts per block
+(models/s3rec.py:62,68) with a mask drawn in the kernel from a fresh 64-bit seed per call — from a generator the
+model owns, seeded from ``torch.initial_seed()``; ``finetune(..., dropout_seed=s)`` fixes it.  ``eval()`` mode is for
+scoring: under ``torch.no_grad()`` it scores, with grad enabled it raises NotImplementedError (as it did before training
+was built; ``train()`` mode with ``dropout_ratio = 0`` is training without dropout).
+
+``pretrain`` / ``encode`` raise NotImplementedError — the reference's own ``encode`` calls
+``_self_attention_block`` without its two mask arguments (models/s3rec.py:117-118), so its pre-training cannot run
+as published and there is nothing to be faithful to.
 
 Supported: embed_size 16 / 32 / 64 / 128, max_seq_len 1 .. 64, 1 .. 4 heads, 1 .. 4 blocks; anything else raises
 NotImplementedError at construction.
@@ -49,6 +59,43 @@ class MultiHeadAttention(nn.Module):
         self.output = nn.Linear(num_heads * embed_size, embed_size)
 
 
+class _FinetuneFn(torch.autograd.Function):
+    """``finetune`` under grad: the stash-keeping encoder and the score launch forward; backward runs the score
+    gradient, the backward kernel, the gradient products / column sums and the item gradient (csrc/s3rec.hip) and
+    hands ``item_embedding.weight``, ``positional_encoding`` and every tensor of ``_block_tensors()`` its gradient."""
+
+    @staticmethod
+    def forward(ctx, model, X, pos_items, neg_items, seed, p, item_emb, pos_enc, *block_tensors):
+        heads, blocks = int(model.cfg.num_heads), int(model.cfg.num_blocks)
+        params = model._params()
+        flag = model._flag()
+        h, ws = engine.s3rec_encode_train(item_emb.detach(), pos_enc.detach(), params, X, heads, blocks, seed=seed, p=p,
+                                          err_flag=flag)
+        pos, neg = engine.s3rec_seq_scores(item_emb.detach(), h, pos_items, neg_items, err_flag=flag)
+        ctx.save_for_backward(X, pos_items, neg_items, h, ws, params, item_emb)
+        ctx.cfg = (heads, blocks, seed, p, flag, [t.shape for t in block_tensors])
+        return pos, neg
+
+    @staticmethod
+    def backward(ctx, gpos, gneg):
+        X, pos_items, neg_items, h, ws, params, item_emb = ctx.saved_tensors
+        heads, blocks, seed, p, flag, shapes = ctx.cfg
+        (B, L), E = X.shape, h.shape[-1]
+        gpos, gneg = gpos.contiguous(), gneg.contiguous()
+        dh = engine.s3rec_score_grad(item_emb.detach(), pos_items, neg_items, gpos, gneg, err_flag=flag)
+        d_emb = engine.s3rec_backward(params, X, dh.view(B, L, E), ws, heads, blocks, seed=seed, p=p)
+        packed = engine.s3rec_param_grads(ws, B, L, E, heads, blocks)
+        d_pos = engine.colsum(d_emb.view(B, L * E)).view(L, E)
+        d_item = torch.zeros_like(item_emb)
+        engine.s3rec_item_grad(X, pos_items, neg_items, d_emb, h, gpos, gneg, d_item, err_flag=flag)
+        grads, at = [], 0
+        for shape in shapes:
+            n = shape.numel()
+            grads.append(packed[at:at + n].view(shape))
+            at += n
+        return (None, None, None, None, None, None, d_item, d_pos, *grads)
+
+
 class S3Rec(BaseModel):
 
     def __init__(self, cfg, num_items, attributes_count):
@@ -75,6 +122,7 @@ class S3Rec(BaseModel):
         self._packed = None
         self._packed_key = None
         self._err_flag = None
+        self._dropout_gen = None
 
     def _init_weights(self):
         # reference models/s3rec.py:40-51: direct children, and the Linears directly inside a ModuleList
@@ -124,8 +172,16 @@ class S3Rec(BaseModel):
     def _scoring_only(self, what):
         if self.training or torch.is_grad_enabled():
             raise NotImplementedError(
-                f"S3Rec.{what}: training is not built yet (no backward pass, no dropout): call it in eval() mode "
-                "under torch.no_grad()")
+                f"S3Rec.{what}: training is not built for this entry point (it goes through finetune): call it in "
+                "eval() mode under torch.no_grad()")
+
+    def _dropout_seed(self):
+        """A fresh 64-bit seed per training call from a generator the model owns, seeded from torch.initial_seed()
+        (so utils.set_seed makes runs repeatable)."""
+        if self._dropout_gen is None:
+            self._dropout_gen = torch.Generator().manual_seed(torch.initial_seed())
+        lo, hi = torch.randint(0, 2 ** 32, (2,), generator=self._dropout_gen, dtype=torch.int64).tolist()
+        return (hi << 32) | lo
 
     def _encode(self, X, last_only):
         if X.dim() != 2 or X.shape[1] != self.cfg.max_seq_len:
@@ -135,9 +191,28 @@ class S3Rec(BaseModel):
                                    last_only=last_only, err_flag=self._flag())
 
     # -- reference surface -----------------------------------------------------------------------------
-    def finetune(self, X, pos_items, neg_items):
+    def finetune(self, X, pos_items, neg_items, *, dropout_seed=None):
         # reference models/s3rec.py:89-100 -> two [batch * max_seq_len] score vectors, padded positions included
-        self._scoring_only("finetune")
+        if torch.is_grad_enabled():
+            if not self.item_embedding.weight.is_cuda:
+                raise NotImplementedError("S3Rec.finetune: training is not built for CPU tensors (the kernels run on "
+                                          "the GPU only): move the model and the batch to the device")
+            if not self.training:
+                # the scoring contract from before training existed, which its tests still hold: eval() scores only
+                raise NotImplementedError("S3Rec.finetune: training is not built for eval() mode: call train() to "
+                                          "train (dropout_ratio = 0 trains without dropout), or score under "
+                                          "torch.no_grad()")
+            if X.dim() != 2 or X.shape[1] != self.cfg.max_seq_len:
+                raise ValueError(f"S3Rec: X must be [batch, max_seq_len = {self.cfg.max_seq_len}], got {tuple(X.shape)}")
+            p = float(self.cfg.dropout_ratio)
+            seed = 0
+            if p > 0.0:
+                seed = self._dropout_seed() if dropout_seed is None else int(dropout_seed)
+            return _FinetuneFn.apply(self, X.contiguous(), pos_items.contiguous(), neg_items.contiguous(), seed, p,
+                                     self.item_embedding.weight, self.positional_encoding, *self._block_tensors())
+        if self.training:
+            raise NotImplementedError("S3Rec.finetune: training is not built under torch.no_grad() (dropout without a "
+                                      "backward pass): call eval() first, or enable grad")
         h = self._encode(X, last_only=False)
         return engine.s3rec_seq_scores(self.item_embedding.weight.detach(), h, pos_items.contiguous(),
                                        neg_items.contiguous(), err_flag=self._flag())

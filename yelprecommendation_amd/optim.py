@@ -56,6 +56,7 @@ class Adam(_DenseBase):
                     continue
                 st = adam_state(self, p)
                 st["step"] += 1
+                torch.autograd.graph.increment_version(p)      # the kernel writes p in place, behind autograd's back
                 by_step.setdefault(st["step"], []).append(
                     (p.data, g, st["exp_avg"], st["exp_avg_sq"], None, 1 if zero_grad else 0))
             # tables, weight matrices and biases alike: one launch per ADAM_MULTI_MAX tensors instead of ~5 us each
@@ -86,3 +87,4 @@ class SGD(_DenseBase):
                 if g is None:
                     continue
                 engine.sgd_dense(p.data, g, group["lr"], group["weight_decay"], zero_grad=zero_grad)
+                torch.autograd.graph.increment_version(p)      # written in place by the kernel
