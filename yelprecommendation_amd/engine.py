@@ -1422,6 +1422,7 @@ def s3rec_backward(params, X, dh_out, workspace, heads, blocks, seed=0, p=0.0, d
 
 
 S3REC_GRAD_CHUNK_ROWS = 2048
+S3REC_GRAD_STREAM_JOBS = 16     # chunk products from which _s3rec_rows_products deals them to four streams
 
 
 _s3rec_side_streams = {}
@@ -1443,7 +1444,7 @@ def _s3rec_rows_products(jobs):
             chunked.append((parts, out))
             small.extend((D[c * chunk:(c + 1) * chunk], Xm[c * chunk:(c + 1) * chunk], parts[c].view(out.shape))
                          for c in range(parts.shape[0]))
-    if len(small) < 16:
+    if len(small) < S3REC_GRAD_STREAM_JOBS:
         for D, Xm, out in small:
             gemm_f32(D, Xm, transA=True, out=out)
     else:
