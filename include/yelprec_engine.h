@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YR_ENGINE_VERSION 33
+#define YR_ENGINE_VERSION 34
 
 #define YR_ERR_UNSUPPORTED (-1) /* embedding width / option not compiled in   */
 #define YR_ERR_BADARG      (-2) /* null pointer, negative size, misalignment  */
@@ -45,6 +45,10 @@ extern "C" {
 
 #define YR_PULL_USER_PHASE 1 /* yr_bpr_mf_pull_apply: owner pass over the user rows          */
 #define YR_PULL_ITEM_PHASE 2 /* yr_bpr_mf_pull_apply: item pass over [item_row_begin, end) */
+
+#define YR_S3REC_TRAIN 0 /* yr_s3rec_batches: X = row[:-3], Y = row[1:-2], a negative per position */
+#define YR_S3REC_VALID 1 /*                   X = row[:-2], Y = row[2:-1], a negative per position */
+#define YR_S3REC_TEST  2 /*                   X = row[:-1], pos = row[-1], n_neg distinct negatives */
 
 #define YR_OPT_ADAM  0 /* torch.optim.Adam  : grad += wd * p               */
 #define YR_OPT_ADAMW 1 /* torch.optim.AdamW : p *= 1 - lr * wd (decoupled) */
@@ -877,6 +881,33 @@ int yr_s3rec_score_grad(const float *item_emb, const int64_t *pos_items, const i
 int yr_s3rec_item_grad(const int64_t *sorted_ids, const int64_t *order, const float *d_emb, const float *h,
                        const float *dpos_preds, const float *dneg_preds, int64_t rows, int E, int64_t num_items,
                        float *partial, float *d_item, int32_t *err_flag, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Device-side S3Rec sequence batches   (reference data/datasets/s3rec_data_pipeline.py:13-50: split +
+ *   _adjust_seq_len; data/datasets/s3rec_dataset.py:21-57: __getitem__ + _negative_sampling)
+ * For the B users of `users`, from the per-user behaviour rows beh_ptr [num_users + 1] / beh_idx (raw item ids in
+ * [0, num_items), interaction order, repeats allowed) and the per-user avoid values avoid_ptr / avoid_idx (ascending
+ * and duplicate-free inside a user, in the draw space 1..num_items).  With n the row length and cut = 3 / 2 / 1 for
+ * YR_S3REC_TRAIN / VALID / TEST: X = row[0, max(0, n - cut)) and Y = row[4 - cut, n - cut + 1) (empty when the start
+ * is not below the end), of each the last L entries, left padded, ids + 1 so that 0 is the pad.
+ *   TRAIN / VALID (n_neg must equal L): X [B][L], pos [B][L] = Y, neg [B][L]: per position j, pads included, 1 + the
+ *     first draw d = 0, 1, ... of element t = user L + j that is not avoided; after 4,096 rejected draws the next free
+ *     value after the last draw, walking 1..num_items cyclically.
+ *   TEST (0 <= n_neg <= 128): X [B][L], pos [B] = Y[L - 1], neg [B][n_neg]: the first n_neg of the candidates
+ *     1 + draw(user, d), d < 4,096, that are neither avoided nor equal to an earlier accepted one, in stream order;
+ *     the rest from an ascending scan of 1..num_items.  One 64-lane wave per user.
+ *   Nothing free: 0 and YR_FLAG_BAD_ITEM (the reference would loop forever).  The draw is yr_triplet_sample's
+ *   (Philox4x32-7 keyed by (seed, epoch), Lemire's multiply-shift over num_items).
+ * A user's rows are a pure function of (seed, epoch, mode, user): any batch equals the same rows of the whole epoch.
+ * A user id outside [0, num_users) raises YR_FLAG_BAD_USER and gets zero rows (nothing is dereferenced); a behaviour
+ * id outside [0, num_items) raises YR_FLAG_BAD_ITEM and reads as the pad.
+ * Checked before any launch: negative sizes, L <= 0, n_neg != L in TRAIN / VALID: YR_ERR_BADARG; n_neg > 128,
+ * num_items > 2^32 - 1, an unknown mode: YR_ERR_UNSUPPORTED; then B == 0: 0; then null pointers: YR_ERR_BADARG.
+ * ------------------------------------------------------------------------- */
+int yr_s3rec_batches(const int64_t *beh_ptr, const int64_t *beh_idx, const int64_t *avoid_ptr,
+                     const int64_t *avoid_idx, int64_t num_users, int64_t num_items, const int64_t *users, int64_t B,
+                     int L, int mode, int n_neg, uint64_t seed, uint64_t epoch, int64_t *X, int64_t *pos,
+                     int64_t *neg, int32_t *err_flag, void *stream);
 
 #ifdef __cplusplus
 }

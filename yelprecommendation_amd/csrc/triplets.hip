@@ -14,7 +14,7 @@
 //             not in the user's sorted avoid-list (binary search)
 // Integer work: the CPU statement oracle/triplet_sampler.py gives the same words bit for bit.
 #include "common.h"
-#include "philox.h"
+#include "sample.h"
 
 namespace yr {
 
@@ -37,8 +37,6 @@ __device__ __forceinline__ uint64_t feistel(uint64_t x, int half_bits, uint32_t 
   return ((uint64_t)L << half_bits) | R;
 }
 
-constexpr int kMaxDraws = 4096;   // after this many rejected draws the first free item >= the last draw is taken
-
 __global__ __launch_bounds__(kBlock) void triplet_sample_kernel(
     const int64_t* __restrict__ row_user, const int64_t* __restrict__ row_item, int64_t n_rows,
     const int64_t* __restrict__ avoid_ptr, const int64_t* __restrict__ avoid_idx, int64_t num_users,
@@ -47,8 +45,7 @@ __global__ __launch_bounds__(kBlock) void triplet_sample_kernel(
     int32_t* __restrict__ err_flag) {
   const uint32_t k0 = fmix32((uint32_t)seed ^ 0x243F6A88u) ^ (uint32_t)epoch;
   const uint32_t k1 = fmix32((uint32_t)(seed >> 32) ^ 0x85A308D3u) ^ (uint32_t)(epoch >> 32) ^ fmix32((uint32_t)epoch);
-  const uint2 key = make_uint2((uint32_t)seed ^ (uint32_t)(epoch * 0x9E3779B97F4A7C15ull >> 32),
-                               (uint32_t)(seed >> 32) ^ (uint32_t)epoch);
+  const uint2 key = sample_key(seed, epoch);
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) {
     const int64_t t = first + i;
@@ -65,25 +62,8 @@ __global__ __launch_bounds__(kBlock) void triplet_sample_kernel(
     }
     const int64_t lo0 = avoid_ptr[u], hi0 = avoid_ptr[u + 1];
     for (int d = 0;; ++d) {
-      // unbiased integer in [0, num_items): Lemire's multiply-shift with rejection of the short first interval
-      const uint4 w = philox4x32<7>(make_uint4((uint32_t)t, (uint32_t)((uint64_t)t >> 32), (uint32_t)d, 0u), key);
-      const uint32_t n32 = (uint32_t)num_items;
-      uint64_t m = (uint64_t)w.x * n32;
-      if ((uint32_t)m < n32) {
-        const uint32_t thr = (0u - n32) % n32;
-        const uint32_t alt[3] = {w.y, w.z, w.w};
-        int a = 0;
-        while ((uint32_t)m < thr && a < 3) m = (uint64_t)alt[a++] * n32;
-      }
-      neg = (int64_t)(m >> 32);
-      // member of the user's avoid list (ascending)?
-      int64_t lo = lo0, hi = hi0;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (avoid_idx[mid] < neg) lo = mid + 1; else hi = mid;
-      }
-      const bool taken = lo < hi0 && avoid_idx[lo] == neg;
-      if (!taken) break;
+      neg = (int64_t)sample_draw((uint64_t)t, (uint32_t)d, (uint32_t)num_items, key);
+      if (!sorted_contains(avoid_idx, lo0, hi0, neg)) break;
       if (d + 1 >= kMaxDraws) {
         // a user whose avoid list covers (almost) the whole catalogue: walk to the next free item
         // (the reference would loop forever on a full list; here: flag and emit item 0)
@@ -91,12 +71,7 @@ __global__ __launch_bounds__(kBlock) void triplet_sample_kernel(
         while (steps < num_items) {
           c = c + 1 == num_items ? 0 : c + 1;
           ++steps;
-          int64_t l2 = lo0, h2 = hi0;
-          while (l2 < h2) {
-            const int64_t mid = (l2 + h2) >> 1;
-            if (avoid_idx[mid] < c) l2 = mid + 1; else h2 = mid;
-          }
-          if (!(l2 < hi0 && avoid_idx[l2] == c)) break;
+          if (!sorted_contains(avoid_idx, lo0, hi0, c)) break;
         }
         if (steps >= num_items) {
           if (err_flag) atomicOr(err_flag, YR_FLAG_BAD_ITEM);

@@ -1537,3 +1537,38 @@ def s3rec_item_grad(X, pos_items, neg_items, d_emb, h, dpos, dneg, d_item, err_f
                                  _dev(d_item, f32, "d_item"), _opt(err_flag, torch.int32, "flag"), _stream()),
           "yr_s3rec_item_grad")
     return d_item
+
+
+S3REC_MODES = {"train": 0, "valid": 1, "test": 2}          # YR_S3REC_TRAIN / VALID / TEST
+S3REC_MAX_NEG = 128
+
+
+def s3rec_batches(beh_ptr, beh_idx, avoid_ptr, avoid_idx, num_items, users, L, mode, seed, epoch, n_neg=None,
+                  err_flag=None):
+    """The S3Rec batch rows of ``users`` (csrc/s3rec_batches.hip; reference s3rec_data_pipeline.py:13-50 +
+    s3rec_dataset.py:21-57), int64 on the device: ``mode`` 'train' / 'valid' gives (X [B, L], pos_items [B, L],
+    neg_items [B, L]), 'test' gives (X [B, L], pos_item [B], neg_items [B, n_neg]) with ``n_neg`` <= 128 mutually
+    distinct negatives.  A user's rows are a pure function of (seed, epoch, mode, user)."""
+    lib = _lib.load()
+    if mode not in S3REC_MODES:
+        raise EngineError(f"s3rec_batches: unknown mode {mode!r}")
+    i64 = torch.int64
+    num_users, B, L = beh_ptr.numel() - 1, users.numel(), int(L)
+    if avoid_ptr.numel() != num_users + 1:
+        raise EngineError("s3rec_batches: beh_ptr and avoid_ptr must both hold num_users + 1 offsets")
+    test = mode == "test"
+    n_neg = (99 if test else L) if n_neg is None else int(n_neg)
+    dev = beh_ptr.device
+    X = torch.empty((B, L), dtype=i64, device=dev)
+    pos = torch.empty((B,) if test else (B, L), dtype=i64, device=dev)
+    neg = torch.empty((B, max(n_neg, 0)), dtype=i64, device=dev)
+    # an empty CSR has no storage to point at: its offsets array stands in (never dereferenced: every row is empty)
+    idx_or = lambda idx, ptr, name: _dev(idx, i64, name) if idx.numel() else _dev(ptr, i64, name)
+    check(lib.yr_s3rec_batches(_dev(beh_ptr, i64, "beh_ptr"), idx_or(beh_idx, beh_ptr, "beh_idx"),
+                               _dev(avoid_ptr, i64, "avoid_ptr"), idx_or(avoid_idx, avoid_ptr, "avoid_idx"),
+                               num_users, int(num_items), _dev(users, i64, "users"), B, L, S3REC_MODES[mode], n_neg,
+                               int(seed) & (2**64 - 1), int(epoch) & (2**64 - 1),
+                               X.data_ptr() if B else None, pos.data_ptr() if B else None,
+                               neg.data_ptr() if neg.numel() else None, _opt(err_flag, torch.int32, "err_flag"),
+                               _stream()), "yr_s3rec_batches")
+    return X, pos, neg

@@ -1,10 +1,11 @@
 """Entry point — counterpart of reference train.py:74-204 for the models on the accelerated path
-(MF, NGCF, CDAE, DCN).  hydra / wandb are not required: the config is ``configs/train_config.yaml`` in
+(MF, NGCF, CDAE, DCN, S3Rec fine-tuning).  hydra / wandb are not required: the config is ``configs/train_config.yaml`` in
 the reference's layout (or the built-in defaults) plus ``key=value`` overrides.
 
     python -m yelprecommendation_amd.train model_name=MF data_dir=data/ epochs=5 batch_size=4096
     python -m yelprecommendation_amd.train model_name=MF synthetic=yelp2018 fast_loader=true
     python -m yelprecommendation_amd.train model_name=DCN synthetic=yelp2018 fast_loader=true hidden_dims=[64,32]
+    python -m yelprecommendation_amd.train model_name=S3Rec synthetic=yelp2018 fast_loader=true batch_size=256
 
 Call order is the reference's: pipeline.preprocess() -> split() -> datasets -> set_seed() ->
 DataLoaders -> trainer.run() -> load_best_model() -> evaluate(test).
@@ -58,8 +59,11 @@ def build(cfg):
     elif cfg.model_name == 'DCN':
         from .data.datasets.dcn_data_pipeline import DCNDataPipeline
         pipe = DCNDataPipeline(cfg)
+    elif cfg.model_name == 'S3Rec':
+        from .data.datasets.s3rec_data_pipeline import S3RecDataPipeline
+        pipe = S3RecDataPipeline(cfg)
     else:
-        raise ValueError(f"model '{cfg.model_name}' is not on the accelerated path (MF, NGCF, CDAE, DCN)")
+        raise ValueError(f"model '{cfg.model_name}' is not on the accelerated path (MF, NGCF, CDAE, DCN, S3Rec)")
     synthetic = cfg.get("synthetic")
     if synthetic:
         from .data.synthetic import make_frame
@@ -77,7 +81,7 @@ def build(cfg):
             nu, ni, mean = (float(x) for x in str(synthetic).split("x"))
             df = make_frame(int(nu), int(ni), mean)
         pipe._load_df = lambda: df
-        if cfg.model_name == 'DCN':
+        if cfg.model_name in ('DCN', 'S3Rec'):
             # the attributes of the synthetic catalogue, in the schema of yelp_item2attributes.json
             from .data.synthetic import make_item_attributes
             attrs = make_item_attributes(int(df.business_id.max()) + 1)
@@ -103,6 +107,15 @@ def build(cfg):
         args.valid_dataset = CDAEDataset(valid_data, 'valid', neg_times=cfg.neg_times)
         args.test_dataset = CDAEDataset(test_data, 'test')
         args.model_info = {'num_items': len(df.columns) - 1, 'num_users': len(train_data)}
+    elif cfg.model_name == 'S3Rec':
+        # reference train.py:178-184
+        from .data.datasets.s3rec_dataset import S3RecDataset
+        train_data, valid_data, test_data = pipe.split(df)
+        attrs = (pipe.item2attributes, pipe.attributes_count)
+        args.train_dataset = S3RecDataset(train_data, *attrs, num_items=pipe.num_items)
+        args.valid_dataset = S3RecDataset(valid_data, *attrs, num_items=pipe.num_items)
+        args.test_dataset = S3RecDataset(test_data, *attrs, num_items=pipe.num_items, train=False)
+        args.model_info = {'num_items': pipe.num_items, 'num_users': pipe.num_users}
     else:
         train_data, valid_data, valid_eval_data, test_eval_data = pipe.split(df)
         args.train_dataset = MFDataset(train_data, num_items=pipe.num_items)
@@ -132,6 +145,8 @@ def train(cfg, args):
     """reference train.py:74-115."""
     from .trainers.mf_trainer import MFTrainer
     from .trainers.ngcf_trainer import NGCFTrainer
+    if cfg.model_name == 'S3Rec':
+        return _train_s3rec(cfg, args)
     if cfg.get("fast_loader") and cfg.model_name in ('MF', 'NGCF', 'DCN'):
         # device-side epoch sampler instead of DataLoader(MFDataset): same distribution, own RNG
         from .data.triplets import EpochLoader
@@ -175,6 +190,30 @@ def train(cfg, args):
     trainer.run(train_dataloader, valid_dataloader, args.valid_eval_data)
     trainer.load_best_model()
     return trainer, trainer.evaluate(args.test_eval_data, 'test')
+
+
+def _train_s3rec(cfg, args):
+    """reference train.py:104-115: fine-tuning (the pre-training of :105-109 is not built)."""
+    if cfg.get("pretrain"):
+        raise NotImplementedError("S3Rec pre-training is not built (pretrain=true): only fine-tuning runs here; a "
+                                  "best_pretrain_model.pt in model_dir is loaded when load_pretrain is set")
+    from .trainers.s3rec_trainer import S3RecTrainer
+    if cfg.get("fast_loader"):
+        # device-side batch builder instead of DataLoader(S3RecDataset): same law, own RNG
+        import torch
+        from .data.s3rec_batches import S3RecBatchLoader
+        store = args.train_dataset.to_sequences(torch.device(cfg.device), cfg.max_seq_len, seed=cfg.seed)
+        mk = lambda mode, seed: S3RecBatchLoader(store, mode, cfg.batch_size, shuffle=cfg.shuffle, seed=seed)
+        train_dataloader, valid_dataloader, test_dataloader = mk('train', cfg.seed), mk('valid', cfg.seed + 1), mk('test', 0)
+    else:
+        train_dataloader = DataLoader(args.train_dataset, batch_size=cfg.batch_size, shuffle=cfg.shuffle)
+        valid_dataloader = DataLoader(args.valid_dataset, batch_size=cfg.batch_size, shuffle=cfg.shuffle)
+        test_dataloader = DataLoader(args.test_dataset, batch_size=cfg.batch_size)
+    trainer = S3RecTrainer(cfg, args.model_info['num_items'], args.data_pipeline.item2attributes,
+                           args.data_pipeline.attributes_count)
+    trainer.run(train_dataloader, valid_dataloader)
+    trainer.load_best_model()
+    return trainer, trainer.evaluate(test_dataloader)
 
 
 def run(cfg, args):

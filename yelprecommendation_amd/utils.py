@@ -60,6 +60,8 @@ DEFAULTS = Config(
         MF=dict(embed_size=64),
         NGCF=dict(embed_size=64, num_orders=2),
         DCN=dict(embed_size=64, hidden_dims=[1024, 1024], cross_orders=1),
+        S3Rec=dict(embed_size=64, max_seq_len=50, num_heads=2, num_blocks=2, pretrain=False, load_pretrain=True,
+                   pretrain_epochs=100, mask_portion=0.2, dropout_ratio=0.1),
     ),
 )
 
