@@ -56,11 +56,11 @@ BUDGETS = [
     (r"void yr::adam_flat_kernel<(true|false), true>", 64, 1024,
      "streaming pass with a barrier per chunk for marked rows of 512 / 1,024 floats: eight waves per SIMD, as the plain form"),
     # S3Rec scoring: the LDS tiles are dynamic (13 KB at E = 16, L <= 32 up to 146 KB at E = 128, L > 32), none static
-    (r"void yr::s3rec_encode_kernel<(16|32|64|128)>", 256, 1024,
+    (r"void yr::s3rec_encode_kernel<(16|32|64|128), false>", 256, 1024,
      "a workgroup per sequence, LDS-bound: one to two workgroups of four waves per CU at the reference's shapes "
      "(81.5 KB at E = 64, L = 50), so two waves per SIMD (512 / 2 -> 256) is all the registers have to allow"),
     (r"yr::s3rec_scores_kernel", 64, 0, "16 lanes per dot product, streaming: eight waves per SIMD"),
-    (r"void yr::s3rec_encode_train_kernel<(16|32|64|128)>", 256, 1024,
+    (r"void yr::s3rec_encode_kernel<(16|32|64|128), true>", 256, 1024,
      "S3Rec training forward: a workgroup per sequence and LDS-bound like the scoring encoder, two waves per SIMD"),
     (r"void yr::s3rec_backward_kernel<(16|32|64|128)>", 512, 1024,
      "S3Rec backward: the same tiles plus one row of floats; at the reference's shape (81.7 KB at E = 64, L = 50) LDS "

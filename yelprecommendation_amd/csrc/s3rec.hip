@@ -1,8 +1,8 @@
-// S3Rec scoring kernels for gfx950 (MI355X): the self-attention encoder of reference models/s3rec.py:53-71,184-214
-// in eval() mode, fused from the embedding gather to the last LayerNorm, and the two score forms of
-// models/s3rec.py:73-115 (finetune: every position; evaluate: the last position against a candidate list).
-// The training kernels (the same encoder with dropout and a stash, its backward pass, the score and item gradients)
-// follow under "training" below.
+// S3Rec kernels for gfx950 (MI355X): the self-attention encoder of reference models/s3rec.py:53-71,184-214, fused
+// from the embedding gather to the last LayerNorm, in eval() mode (scoring) and in train() mode (dropout and a stash,
+// see "what train() mode adds" below): one kernel text, s3rec_encode_kernel<E, TRAIN>; the two score forms of
+// models/s3rec.py:73-115 (finetune: every position; evaluate: the last position against a candidate list); and, under
+// "backward" below, the encoder's backward pass and the score and item gradients.
 //
 // Encoder: one workgroup (4 waves) per sequence.  The sequence's activations never leave the CU: five LDS tiles
 //   sH [LP][E + 1]   h, the block's input (both residuals add it: models/s3rec.py:64,70), then the block's output
@@ -90,33 +90,15 @@ __device__ __forceinline__ f32x16 mma_lds(const float* A, int pa, const float* B
 // element q of a lane's accumulators is (row, col) of the 32 x 32 tile
 __device__ __forceinline__ int acc_row(int q, int lane) { return (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5); }
 
-// dst[i][:] = LayerNorm(src[i][:]) (biased variance) for the rows of this wave
-template <int E>
-__device__ __forceinline__ void layernorm_rows(const float* src, float* dst, int P, int rows, const float* __restrict__ g,
-                                               const float* __restrict__ b, int lane, int wave) {
-  constexpr int EPL = E > kWave ? E / kWave : 1;
-  for (int i = wave; i < rows; i += kWavesPerBlock) {
-    float x[EPL], s = 0.0f;
-#pragma unroll
-    for (int t = 0; t < EPL; ++t) {
-      const int e = lane + kWave * t;
-      x[t] = e < E ? src[i * P + e] : 0.0f;
-      s += x[t];
-    }
-    const float mean = wave_sum(s) / (float)E;
-    float v = 0.0f;
-#pragma unroll
-    for (int t = 0; t < EPL; ++t) {
-      const int e = lane + kWave * t;
-      const float d = e < E ? x[t] - mean : 0.0f;
-      v += d * d;
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)E + kS3LnEps);
-#pragma unroll
-    for (int t = 0; t < EPL; ++t) {
-      const int e = lane + kWave * t;
-      if (e < E) dst[i * P + e] = (x[t] - mean) * rstd * g[e] + b[e];
-    }
+// P = softmax over the keys j <= i of S / sqrt(E), in place, a wave per row; the keys j > i get exactly 0
+__device__ __forceinline__ void softmax_causal_rows(float* sS, int PS, int LP, float sqrtE, int lane, int wave) {
+  for (int i = wave; i < LP; i += kWavesPerBlock) {
+    const bool on = lane <= i;
+    const float v = on ? sS[i * PS + lane] / sqrtE : -INFINITY;
+    const float mx = wave_max(v);
+    const float ex = on ? expf(v - mx) : 0.0f;
+    const float sum = wave_sum(ex);
+    if (lane < LP) sS[i * PS + lane] = ex / sum;
   }
 }
 
@@ -125,221 +107,10 @@ inline size_t s3rec_lds_bytes(int E, int L) {
   return (size_t)(4 * LP * (E + 1) + LP * (LP + 1) + LP) * sizeof(float);
 }
 
-template <int E>
-__global__ __launch_bounds__(kBlock) void s3rec_encode_kernel(S3Enc p) {
-  extern __shared__ float s3_lds[];
-  constexpr int P = E + 1;
-  constexpr int NT = E >= 32 ? E / 32 : 1;          // column tiles of an [LP][E] result
-  const int L = p.L, H = p.heads;
-  const int LP = L > 32 ? 64 : 32, MT = LP / 32, PS = LP + 1;
-  const int ntile = MT * NT;                         // <= 8: two per wave
-  float* sH = s3_lds;
-  float* sQ = sH + LP * P;
-  float* sK = sQ + LP * P;
-  float* sV = sK + LP * P;
-  float* sS = sV + LP * P;
-  float* sPad = sS + LP * PS;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const int r = lane & 31;
-  const float sqrtE = sqrtf((float)E);
-  const int64_t EE = (int64_t)E * E;
-  const int64_t block_stride = (4 * H + 2) * EE + 7 * E;
-
-  for (int64_t seq = blockIdx.x; seq < p.B; seq += gridDim.x) {
-    // h = item_embedding[X] + positional_encoding (the positional row at padded positions too)
-    const int64_t* X = p.X + seq * L;
-    int flag = 0;
-    for (int e = tid; e < LP * E; e += kBlock) {
-      const int i = e / E, d = e - i * E;
-      float v = 0.0f;
-      if (i < L) {
-        const int64_t id = X[i];
-        if (id >= 0 && id <= p.num_items) v = p.item_emb[id * E + d];
-        else flag = YR_FLAG_BAD_ITEM;
-        v += p.pos[i * E + d];
-      }
-      sH[i * P + d] = v;
-    }
-    if (tid < LP) sPad[tid] = (tid < L && X[tid] > 0) ? 0.0f : 1.0f;
-    if (flag && p.err_flag) atomicOr(p.err_flag, flag);
-    __syncthreads();
-
-    for (int blk = 0; blk < p.blocks; ++blk) {
-      const float* Wq = p.params + blk * block_stride;
-      const float* Wo = Wq + 3 * H * EE;
-      const float* bo = Wo + H * EE;
-      const float *g1 = bo + E, *be1 = g1 + E;
-      const float* W1 = be1 + E;
-      const float* b1 = W1 + EE;
-      const float* W2 = b1 + E;
-      const float* b2 = W2 + EE;
-      const float *g2 = b2 + E, *be2 = g2 + E;
-
-      f32x16 oacc[2] = {zero16(), zero16()};          // attn tiles wave, wave + 4 across the heads
-      for (int h = 0; h < H; ++h) {
-        // Q, K, V of head h: 3 ntile tiles dealt to the waves
-        for (int w = wave; w < 3 * ntile; w += kWavesPerBlock) {
-          const int m = w / ntile, t = w - m * ntile, it = t / NT, jt = t - it * NT;
-          const float* W = Wq + (m * H + h) * EE + (int64_t)jt * 32 * E;
-          const f32x16 acc = mma_weights<E>(sH + it * 32 * P, P, W, E, E - jt * 32, zero16(), lane);
-          float* dst = m == 0 ? sQ : m == 1 ? sK : sV;
-          const int col = jt * 32 + r;
-          if (col < E) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-              const int row = it * 32 + acc_row(q, lane);
-              dst[row * P + col] = m == 1 ? acc[q] * sPad[row] : acc[q];
-            }
-          }
-        }
-        __syncthreads();
-        // S = Q K^T on and below the diagonal tiles
-        for (int w = wave; w < MT * (MT + 1) / 2; w += kWavesPerBlock) {
-          const int it = w == 0 ? 0 : 1, jt = w == 2 ? 1 : 0;
-          const f32x16 acc = mma_lds(sQ + it * 32 * P, P, sK + jt * 32 * P, P, 1, 32, E, zero16(), lane);
-#pragma unroll
-          for (int q = 0; q < 16; ++q) sS[(it * 32 + acc_row(q, lane)) * PS + jt * 32 + r] = acc[q];
-        }
-        __syncthreads();
-        // P = softmax over the keys j <= i of S / sqrt(E); the keys j > i get exactly 0
-        for (int i = wave; i < LP; i += kWavesPerBlock) {
-          const bool on = lane <= i;
-          const float v = on ? sS[i * PS + lane] / sqrtE : -INFINITY;
-          const float mx = wave_max(v);
-          const float ex = on ? expf(v - mx) : 0.0f;
-          const float sum = wave_sum(ex);
-          if (lane < LP) sS[i * PS + lane] = ex / sum;
-        }
-        __syncthreads();
-        // A_h = P V into sQ
-        for (int t = wave; t < ntile; t += kWavesPerBlock) {
-          const int it = t / NT, jt = t - it * NT;
-          const f32x16 acc = mma_lds(sS + it * 32 * PS, PS, sV + jt * 32, 1, P, E - jt * 32, (it + 1) * 32, zero16(), lane);
-          const int col = jt * 32 + r;
-          if (col < E) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) sQ[(it * 32 + acc_row(q, lane)) * P + col] = acc[q];
-          }
-        }
-        __syncthreads();
-        // attn += A_h W_o[:, hE:(h+1)E]^T
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int t = wave + kWavesPerBlock * u;
-          if (t < ntile) {
-            const int it = t / NT, jt = t - it * NT;
-            oacc[u] = mma_weights<E>(sQ + it * 32 * P, P, Wo + (int64_t)jt * 32 * H * E + h * E, (int64_t)H * E,
-                                     E - jt * 32, oacc[u], lane);
-          }
-        }
-        __syncthreads();
-      }
-      // h + attn + b_o -> sK, x1 = LayerNorm1 -> sV
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int t = wave + kWavesPerBlock * u;
-        const int it = t / NT, jt = t - it * NT, col = jt * 32 + r;
-        if (t < ntile && col < E) {
-          const float bias = bo[col];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const int row = it * 32 + acc_row(q, lane);
-            sK[row * P + col] = sH[row * P + col] + (oacc[u][q] + bias);
-          }
-        }
-      }
-      __syncthreads();
-      layernorm_rows<E>(sK, sV, P, LP, g1, be1, lane, wave);
-      __syncthreads();
-      // relu(W_1 x1 + b_1) -> sQ
-      for (int t = wave; t < ntile; t += kWavesPerBlock) {
-        const int it = t / NT, jt = t - it * NT, col = jt * 32 + r;
-        const f32x16 acc = mma_weights<E>(sV + it * 32 * P, P, W1 + (int64_t)jt * 32 * E, E, E - jt * 32, zero16(), lane);
-        if (col < E) {
-          const float bias = b1[col];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) sQ[(it * 32 + acc_row(q, lane)) * P + col] = fmaxf(acc[q] + bias, 0.0f);
-        }
-      }
-      __syncthreads();
-      // h + W_2 (.) + b_2 -> sK (the reference adds the block's INPUT here, not x1), LayerNorm2 -> sH
-      for (int t = wave; t < ntile; t += kWavesPerBlock) {
-        const int it = t / NT, jt = t - it * NT, col = jt * 32 + r;
-        const f32x16 acc = mma_weights<E>(sQ + it * 32 * P, P, W2 + (int64_t)jt * 32 * E, E, E - jt * 32, zero16(), lane);
-        if (col < E) {
-          const float bias = b2[col];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const int row = it * 32 + acc_row(q, lane);
-            sK[row * P + col] = sH[row * P + col] + (acc[q] + bias);
-          }
-        }
-      }
-      __syncthreads();
-      layernorm_rows<E>(sK, sH, P, LP, g2, be2, lane, wave);
-      __syncthreads();
-    }
-
-    if (p.last_only) {
-      for (int d = tid; d < E; d += kBlock) p.out[seq * E + d] = sH[(L - 1) * P + d];
-    } else {
-      float* out = p.out + seq * L * E;
-      for (int e = tid; e < L * E; e += kBlock) {
-        const int i = e / E;
-        out[e] = sH[i * P + (e - i * E)];
-      }
-    }
-    __syncthreads();                                  // the next sequence overwrites sH
-  }
-}
-
-// out_a[r] = <I[items_a[r]], h[r / per_a]> for r < rows_a and the same for list b: 16 lanes per row.  A bad id
-// raises the flag and scores 0.
-struct S3Scores {
-  const float* item_emb;
-  const float* h;
-  const int64_t *items_a, *items_b;
-  int64_t rows_a, rows_b, per_a, per_b, num_items;
-  int E;
-  float *out_a, *out_b;
-  int32_t* err_flag;
-};
-
-__global__ __launch_bounds__(kBlock) void s3rec_scores_kernel(S3Scores p) {
-  constexpr int LPR = 16;
-  const int sub = threadIdx.x & (LPR - 1);
-  const int64_t rows = p.rows_a + p.rows_b;
-  const int64_t rounds = (rows + kBlock / LPR - 1) / (kBlock / LPR);
-  int flag = 0;
-  // whole rounds, so that the 16 lanes of a row stay together in the shuffles
-  for (int64_t rd = blockIdx.x; rd < rounds; rd += gridDim.x) {
-    const int64_t row = rd * (kBlock / LPR) + threadIdx.x / LPR;
-    float s = 0.0f;
-    bool ok = false;
-    const bool a = row < p.rows_a;
-    const int64_t ra = a ? row : row - p.rows_a;
-    if (row < rows) {
-      const int64_t id = a ? p.items_a[ra] : p.items_b[ra];
-      ok = id >= 0 && id <= p.num_items;
-      if (ok) {
-        const float* e = p.item_emb + id * p.E;
-        const float* hr = p.h + (ra / (a ? p.per_a : p.per_b)) * p.E;
-        for (int d = sub; d < p.E; d += LPR) s += e[d] * hr[d];
-      } else {
-        flag = YR_FLAG_BAD_ITEM;
-      }
-    }
-    s = group_sum<LPR>(s);
-    if (row < rows && sub == 0) (a ? p.out_a : p.out_b)[ra] = s;
-  }
-  if (flag && p.err_flag) atomicOr(p.err_flag, flag);
-}
-
-
-// ================================================================================================ training
-// The training forward (s3rec_encode_train_kernel) is the encoder above with dropout at the two sites of a block
-// (reference models/s3rec.py:62,68: after W_o + b_o and after W_2 + b_2, before the residual) and a stash in global
-// memory of what the backward consumes; the backward (s3rec_backward_kernel) walks the blocks in reverse, again one
+// ========================================================== the encoder (both modes) and what train() mode adds
+// s3rec_encode_kernel<E, true> adds to the encoder dropout at the two sites of a block (reference
+// models/s3rec.py:62,68: after W_o + b_o and after W_2 + b_2, before the residual) and a stash in global memory of
+// what the backward consumes; the backward (s3rec_backward_kernel) walks the blocks in reverse, again one
 // workgroup per sequence and nothing reduced across workgroups: it leaves, per block, the delta tensors whose
 // transposed products with the stash are the weight gradients (yr_gemm_f32 transA = 1) and whose column sums are
 // the bias / LayerNorm gradients (yr_colsum).
@@ -441,12 +212,12 @@ __device__ __forceinline__ f32x16 mma_lds_s(const float* A, int ai, int ak, cons
   return acc;
 }
 
-// layernorm_rows with the arithmetic in the same order, which also stores the normalised value, rstd and (y_out
-// given) the result for the rows < L of this sequence
-template <int E>
-__device__ __forceinline__ void layernorm_rows_train(const float* src, float* dst, int P, int rows, int L,
-                                                     const float* __restrict__ g, const float* __restrict__ b,
-                                                     float* xh_out, float* rstd_out, float* y_out, int lane, int wave) {
+// dst[i][:] = LayerNorm(src[i][:]) (biased variance) for the rows of this wave.  STASH: also stores the normalised
+// value, rstd and (y_out given) the result for the rows < L of this sequence; otherwise the three pointers are unused
+template <int E, bool STASH>
+__device__ __forceinline__ void layernorm_rows(const float* src, float* dst, int P, int rows, int L,
+                                               const float* __restrict__ g, const float* __restrict__ b, float* xh_out,
+                                               float* rstd_out, float* y_out, int lane, int wave) {
   constexpr int EPL = E > kWave ? E / kWave : 1;
   for (int i = wave; i < rows; i += kWavesPerBlock) {
     float x[EPL], s = 0.0f;
@@ -465,7 +236,7 @@ __device__ __forceinline__ void layernorm_rows_train(const float* src, float* ds
       v += d * d;
     }
     const float rstd = 1.0f / sqrtf(wave_sum(v) / (float)E + kS3LnEps);
-    if (i < L && lane == 0) rstd_out[i * 4] = rstd;
+    if (STASH && i < L && lane == 0) rstd_out[i * 4] = rstd;
 #pragma unroll
     for (int t = 0; t < EPL; ++t) {
       const int e = lane + kWave * t;
@@ -473,7 +244,7 @@ __device__ __forceinline__ void layernorm_rows_train(const float* src, float* ds
         const float xh = (x[t] - mean) * rstd;
         const float y = xh * g[e] + b[e];
         dst[i * P + e] = y;
-        if (i < L) {
+        if (STASH && i < L) {
           xh_out[i * E + e] = xh;
           if (y_out) y_out[i * E + e] = y;
         }
@@ -487,15 +258,19 @@ inline size_t s3rec_train_lds_bytes(int E, int L) {
   return s3rec_lds_bytes(E, L) + (size_t)2 * LP * sizeof(float);
 }
 
-template <int E>
-__global__ __launch_bounds__(kBlock, 2) void s3rec_encode_train_kernel(S3Train tp) {
+// The encoder in both modes.  TRAIN = false (yr_s3rec_encode) reads enc alone and honours last_only; TRAIN = true
+// (yr_s3rec_encode_train) stores the stash and drops out where p > 0.  At p = 0 both run the same arithmetic in the
+// same order: `out` is equal bit for bit.  The body is the kernel itself, not a device function under two kernels:
+// a function body is optimised on its own before it is inlined, which moved the registers of all eight instances.
+template <int E, bool TRAIN>
+__global__ __launch_bounds__(kBlock, TRAIN ? 2 : 1) void s3rec_encode_kernel(S3Train tp) {
   extern __shared__ float s3_lds[];
   const S3Enc& p = tp.enc;
   constexpr int P = E + 1;
-  constexpr int NT = E >= 32 ? E / 32 : 1;
+  constexpr int NT = E >= 32 ? E / 32 : 1;          // column tiles of an [LP][E] result
   const int L = p.L, H = p.heads;
   const int LP = L > 32 ? 64 : 32, MT = LP / 32, PS = LP + 1;
-  const int ntile = MT * NT;
+  const int ntile = MT * NT;                         // <= 8: two per wave
   float* sH = s3_lds;
   float* sQ = sH + LP * P;
   float* sK = sQ + LP * P;
@@ -509,9 +284,10 @@ __global__ __launch_bounds__(kBlock, 2) void s3rec_encode_train_kernel(S3Train t
   const int64_t block_stride = (4 * H + 2) * EE + 7 * E;
   const S3Layout lay = s3_layout(p.B * L, E, H);
   const uint2 key = make_uint2((uint32_t)tp.seed, (uint32_t)(tp.seed >> 32));
-  const bool drop = tp.p > 0.0f;
+  const bool drop = TRAIN && tp.p > 0.0f;
 
   for (int64_t seq = blockIdx.x; seq < p.B; seq += gridDim.x) {
+    // h = item_embedding[X] + positional_encoding (the positional row at padded positions too)
     const int64_t row0 = seq * L;
     const int64_t* X = p.X + row0;
     int flag = 0;
@@ -543,15 +319,16 @@ __global__ __launch_bounds__(kBlock, 2) void s3rec_encode_train_kernel(S3Train t
       float* ws = tp.ws + blk * lay.block;
       const int HE = H * E;
 
-      {                                                 // the block's input
+      if (TRAIN) {                                      // the block's input
         float* dst = ws + lay.h_in + row0 * E;
         for (int e = tid; e < L * E; e += kBlock) {
           const int i = e / E;
           dst[e] = sH[i * P + (e - i * E)];
         }
       }
-      f32x16 oacc[2] = {zero16(), zero16()};
+      f32x16 oacc[2] = {zero16(), zero16()};          // attn tiles wave, wave + 4 across the heads
       for (int h = 0; h < H; ++h) {
+        // Q, K, V of head h: 3 ntile tiles dealt to the waves
         for (int w = wave; w < 3 * ntile; w += kWavesPerBlock) {
           const int m = w / ntile, t = w - m * ntile, it = t / NT, jt = t - it * NT;
           const float* W = Wq + (m * H + h) * EE + (int64_t)jt * 32 * E;
@@ -565,11 +342,12 @@ __global__ __launch_bounds__(kBlock, 2) void s3rec_encode_train_kernel(S3Train t
               const int row = it * 32 + acc_row(q, lane);
               const float v = m == 1 ? acc[q] * sPad[row] : acc[q];
               dst[row * P + col] = v;
-              if (row < L) gq[(int64_t)row * 3 * HE + col] = v;
+              if (TRAIN && row < L) gq[(int64_t)row * 3 * HE + col] = v;
             }
           }
         }
         __syncthreads();
+        // S = Q K^T on and below the diagonal tiles
         for (int w = wave; w < MT * (MT + 1) / 2; w += kWavesPerBlock) {
           const int it = w == 0 ? 0 : 1, jt = w == 2 ? 1 : 0;
           const f32x16 acc = mma_lds(sQ + it * 32 * P, P, sK + jt * 32 * P, P, 1, 32, E, zero16(), lane);
@@ -577,15 +355,9 @@ __global__ __launch_bounds__(kBlock, 2) void s3rec_encode_train_kernel(S3Train t
           for (int q = 0; q < 16; ++q) sS[(it * 32 + acc_row(q, lane)) * PS + jt * 32 + r] = acc[q];
         }
         __syncthreads();
-        for (int i = wave; i < LP; i += kWavesPerBlock) {
-          const bool on = lane <= i;
-          const float v = on ? sS[i * PS + lane] / sqrtE : -INFINITY;
-          const float mx = wave_max(v);
-          const float ex = on ? expf(v - mx) : 0.0f;
-          const float sum = wave_sum(ex);
-          if (lane < LP) sS[i * PS + lane] = ex / sum;
-        }
+        softmax_causal_rows(sS, PS, LP, sqrtE, lane, wave);
         __syncthreads();
+        // A_h = P V into sQ
         for (int t = wave; t < ntile; t += kWavesPerBlock) {
           const int it = t / NT, jt = t - it * NT;
           const f32x16 acc = mma_lds(sS + it * 32 * PS, PS, sV + jt * 32, 1, P, E - jt * 32, (it + 1) * 32, zero16(), lane);
@@ -596,11 +368,12 @@ __global__ __launch_bounds__(kBlock, 2) void s3rec_encode_train_kernel(S3Train t
             for (int q = 0; q < 16; ++q) {
               const int row = it * 32 + acc_row(q, lane);
               sQ[row * P + col] = acc[q];
-              if (row < L) ga[(int64_t)row * HE + col] = acc[q];
+              if (TRAIN && row < L) ga[(int64_t)row * HE + col] = acc[q];
             }
           }
         }
         __syncthreads();
+        // attn += A_h W_o[:, hE:(h+1)E]^T
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const int t = wave + kWavesPerBlock * u;
@@ -632,9 +405,10 @@ __global__ __launch_bounds__(kBlock, 2) void s3rec_encode_train_kernel(S3Train t
         dropout_tile<E>(sK, sH, P, L, LP, key, 2 * blk, row0 * E, tp.p, tp.scale, nullptr, tid);
         __syncthreads();
       }
-      layernorm_rows_train<E>(sK, sV, P, LP, L, g1, be1, ws + lay.xh1 + row0 * E, ws + lay.rstd + row0 * 4,
-                              ws + lay.x1 + row0 * E, lane, wave);
+      layernorm_rows<E, TRAIN>(sK, sV, P, LP, L, g1, be1, ws + lay.xh1 + row0 * E, ws + lay.rstd + row0 * 4,
+                               ws + lay.x1 + row0 * E, lane, wave);
       __syncthreads();
+      // relu(W_1 x1 + b_1) -> sQ
       for (int t = wave; t < ntile; t += kWavesPerBlock) {
         const int it = t / NT, jt = t - it * NT, col = jt * 32 + r;
         const f32x16 acc = mma_weights<E>(sV + it * 32 * P, P, W1 + (int64_t)jt * 32 * E, E, E - jt * 32, zero16(), lane);
@@ -646,11 +420,12 @@ __global__ __launch_bounds__(kBlock, 2) void s3rec_encode_train_kernel(S3Train t
             const int row = it * 32 + acc_row(q, lane);
             const float v = fmaxf(acc[q] + bias, 0.0f);
             sQ[row * P + col] = v;
-            if (row < L) gr[row * E + col] = v;
+            if (TRAIN && row < L) gr[row * E + col] = v;
           }
         }
       }
       __syncthreads();
+      // h + dropout(W_2 (.) + b_2) -> sK (the reference adds the block's INPUT here, not x1), LayerNorm2 -> sH
       for (int t = wave; t < ntile; t += kWavesPerBlock) {
         const int it = t / NT, jt = t - it * NT, col = jt * 32 + r;
         const f32x16 acc = mma_weights<E>(sQ + it * 32 * P, P, W2 + (int64_t)jt * 32 * E, E, E - jt * 32, zero16(), lane);
@@ -669,19 +444,67 @@ __global__ __launch_bounds__(kBlock, 2) void s3rec_encode_train_kernel(S3Train t
         dropout_tile<E>(sK, sH, P, L, LP, key, 2 * blk + 1, row0 * E, tp.p, tp.scale, nullptr, tid);
         __syncthreads();
       }
-      layernorm_rows_train<E>(sK, sH, P, LP, L, g2, be2, ws + lay.xh2 + row0 * E, ws + lay.rstd + row0 * 4 + 1, nullptr,
-                              lane, wave);
+      layernorm_rows<E, TRAIN>(sK, sH, P, LP, L, g2, be2, ws + lay.xh2 + row0 * E, ws + lay.rstd + row0 * 4 + 1,
+                               nullptr, lane, wave);
       __syncthreads();
     }
 
-    float* out = p.out + row0 * E;
-    for (int e = tid; e < L * E; e += kBlock) {
-      const int i = e / E;
-      out[e] = sH[i * P + (e - i * E)];
+    if (!TRAIN && p.last_only) {
+      for (int d = tid; d < E; d += kBlock) p.out[seq * E + d] = sH[(L - 1) * P + d];
+    } else {
+      float* out = p.out + row0 * E;
+      for (int e = tid; e < L * E; e += kBlock) {
+        const int i = e / E;
+        out[e] = sH[i * P + (e - i * E)];
+      }
     }
-    __syncthreads();
+    __syncthreads();                                  // the next sequence overwrites sH
   }
 }
+
+// out_a[r] = <I[items_a[r]], h[r / per_a]> for r < rows_a and the same for list b: 16 lanes per row.  A bad id
+// raises the flag and scores 0.
+struct S3Scores {
+  const float* item_emb;
+  const float* h;
+  const int64_t *items_a, *items_b;
+  int64_t rows_a, rows_b, per_a, per_b, num_items;
+  int E;
+  float *out_a, *out_b;
+  int32_t* err_flag;
+};
+
+__global__ __launch_bounds__(kBlock) void s3rec_scores_kernel(S3Scores p) {
+  constexpr int LPR = 16;
+  const int sub = threadIdx.x & (LPR - 1);
+  const int64_t rows = p.rows_a + p.rows_b;
+  const int64_t rounds = (rows + kBlock / LPR - 1) / (kBlock / LPR);
+  int flag = 0;
+  // whole rounds, so that the 16 lanes of a row stay together in the shuffles
+  for (int64_t rd = blockIdx.x; rd < rounds; rd += gridDim.x) {
+    const int64_t row = rd * (kBlock / LPR) + threadIdx.x / LPR;
+    float s = 0.0f;
+    bool ok = false;
+    const bool a = row < p.rows_a;
+    const int64_t ra = a ? row : row - p.rows_a;
+    if (row < rows) {
+      const int64_t id = a ? p.items_a[ra] : p.items_b[ra];
+      ok = id >= 0 && id <= p.num_items;
+      if (ok) {
+        const float* e = p.item_emb + id * p.E;
+        const float* hr = p.h + (ra / (a ? p.per_a : p.per_b)) * p.E;
+        for (int d = sub; d < p.E; d += LPR) s += e[d] * hr[d];
+      } else {
+        flag = YR_FLAG_BAD_ITEM;
+      }
+    }
+    s = group_sum<LPR>(s);
+    if (row < rows && sub == 0) (a ? p.out_a : p.out_b)[ra] = s;
+  }
+  if (flag && p.err_flag) atomicOr(p.err_flag, flag);
+}
+
+// ================================================================================================ backward
 
 // LayerNorm backward of the rows of sG (the gradient g arriving at the LayerNorm's output): stores g and g * xh for
 // the gamma / beta column sums, then d = rstd (dy - mean(dy) - xh mean(dy xh)), dy = g gamma.  ACC: sAcc += d, else
@@ -852,14 +675,7 @@ __global__ __launch_bounds__(kBlock) void s3rec_backward_kernel(S3Train tp) {
           for (int q = 0; q < 16; ++q) sS[(it * 32 + acc_row(q, lane)) * PS + jt * 32 + r] = acc[q];
         }
         __syncthreads();
-        for (int i = wave; i < LP; i += kWavesPerBlock) {
-          const bool on = lane <= i;
-          const float v = on ? sS[i * PS + lane] / sqrtE : -INFINITY;
-          const float mx = wave_max(v);
-          const float ex = on ? expf(v - mx) : 0.0f;
-          const float sum = wave_sum(ex);
-          if (lane < LP) sS[i * PS + lane] = ex / sum;
-        }
+        softmax_causal_rows(sS, PS, LP, sqrtE, lane, wave);
         __syncthreads();
         // dV = P^T dA_h (queries i >= the tile's first key)
         for (int t = wave; t < ntile; t += kWavesPerBlock) {
@@ -1066,36 +882,62 @@ using namespace yr;
 
 static bool s3rec_width_ok(int E) { return E == 16 || E == 32 || E == 64 || E == 128; }
 
-template <int E>
-static int s3rec_launch(const S3Enc& p, hipStream_t stream) {
-  const size_t lds = s3rec_lds_bytes(E, p.L);
-  static bool raised = false;                        // more than the default 64 KB of dynamic LDS: once per process
-  if (!raised && lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&s3rec_encode_kernel<E>),
+// BADARG for a dimension that cannot be, UNSUPPORTED for one past what the per-sequence kernels are built for
+static int s3rec_shape_status(int64_t B, int L, int E, int heads, int blocks) {
+  if (B < 0 || L <= 0 || E <= 0 || heads <= 0 || blocks <= 0) return YR_ERR_BADARG;
+  if (!s3rec_width_ok(E) || L > kS3MaxL || heads > kS3MaxHeads || blocks > kS3MaxBlocks) return YR_ERR_UNSUPPORTED;
+  return 0;
+}
+
+// One of the three per-sequence kernels: the dynamic-LDS raise once per kernel, the launch, its status
+template <auto KERNEL>
+static int s3rec_launch(const S3Train& p, size_t lds, int grid, void* stream) {
+  static bool raised = false;                        // per kernel: this function has one instantiation for each
+  if (!raised && lds > 65536) {                      // more than the default 64 KB of dynamic LDS: once per process
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
     if (e != hipSuccess) return (int)e;
     raised = true;
   }
-  const int grid = (int)std::min<int64_t>(p.B, 1 << 20);
-  hipLaunchKernelGGL(s3rec_encode_kernel<E>, dim3(grid), dim3(kBlock), lds, stream, p);
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(kBlock), lds, (hipStream_t)stream, p);
   return launch_status();
+}
+
+// a workgroup per sequence, the kernel's own loop past 2^20 sequences
+template <bool TRAIN>
+static int s3rec_encode_launch(const S3Train& p, int E, void* stream) {
+  const size_t lds = TRAIN ? s3rec_train_lds_bytes(E, p.enc.L) : s3rec_lds_bytes(E, p.enc.L);
+  const int grid = (int)std::min<int64_t>(p.enc.B, 1 << 20);
+  switch (E) {
+    case 16: return s3rec_launch<&s3rec_encode_kernel<16, TRAIN>>(p, lds, grid, stream);
+    case 32: return s3rec_launch<&s3rec_encode_kernel<32, TRAIN>>(p, lds, grid, stream);
+    case 64: return s3rec_launch<&s3rec_encode_kernel<64, TRAIN>>(p, lds, grid, stream);
+    default: return s3rec_launch<&s3rec_encode_kernel<128, TRAIN>>(p, lds, grid, stream);
+  }
+}
+
+static int s3rec_backward_launch(const S3Train& p, int E, void* stream) {
+  const size_t lds = s3rec_train_lds_bytes(E, p.enc.L);
+  const int grid = (int)std::min<int64_t>(p.enc.B, 1 << 20);
+  switch (E) {
+    case 16: return s3rec_launch<&s3rec_backward_kernel<16>>(p, lds, grid, stream);
+    case 32: return s3rec_launch<&s3rec_backward_kernel<32>>(p, lds, grid, stream);
+    case 64: return s3rec_launch<&s3rec_backward_kernel<64>>(p, lds, grid, stream);
+    default: return s3rec_launch<&s3rec_backward_kernel<128>>(p, lds, grid, stream);
+  }
 }
 
 extern "C" int yr_s3rec_encode(const float* item_emb, const float* pos_enc, const float* params, const int64_t* X,
                                int64_t B, int L, int E, int heads, int blocks, int64_t num_items, int last_only,
                                float* out, int32_t* err_flag, void* stream) {
-  if (B < 0 || L <= 0 || E <= 0 || heads <= 0 || blocks <= 0 || num_items < 0) return YR_ERR_BADARG;
-  if (!s3rec_width_ok(E) || L > kS3MaxL || heads > kS3MaxHeads || blocks > kS3MaxBlocks) return YR_ERR_UNSUPPORTED;
+  if (num_items < 0) return YR_ERR_BADARG;
+  if (const int s = s3rec_shape_status(B, L, E, heads, blocks)) return s;
   if (B == 0) return 0;
   if (!item_emb || !pos_enc || !params || !X || !out) return YR_ERR_BADARG;
   if ((reinterpret_cast<uintptr_t>(params) & 15) != 0) return YR_ERR_BADARG;
-  const S3Enc p{item_emb, pos_enc, params, X, B, num_items, L, heads, blocks, last_only != 0, out, err_flag};
-  switch (E) {
-    case 16: return s3rec_launch<16>(p, (hipStream_t)stream);
-    case 32: return s3rec_launch<32>(p, (hipStream_t)stream);
-    case 64: return s3rec_launch<64>(p, (hipStream_t)stream);
-    default: return s3rec_launch<128>(p, (hipStream_t)stream);
-  }
+  const S3Train t{S3Enc{item_emb, pos_enc, params, X, B, num_items, L, heads, blocks, last_only != 0, out, err_flag},
+                  nullptr, nullptr, 0, 0.0f, 1.0f};
+  return s3rec_encode_launch<false>(t, E, stream);
 }
 
 static int s3rec_scores(const S3Scores& p, hipStream_t stream) {
@@ -1129,40 +971,13 @@ extern "C" int yr_s3rec_candidate_scores(const float* item_emb, const float* h_l
 }
 
 extern "C" int64_t yr_s3rec_train_workspace_floats(int64_t B, int L, int E, int heads, int blocks) {
-  if (B < 0 || L <= 0 || E <= 0 || heads <= 0 || blocks <= 0) return YR_ERR_BADARG;
-  if (!s3rec_width_ok(E) || L > kS3MaxL || heads > kS3MaxHeads || blocks > kS3MaxBlocks) return YR_ERR_UNSUPPORTED;
+  if (const int s = s3rec_shape_status(B, L, E, heads, blocks)) return s;
   return blocks * s3_layout(B * L, E, heads).block;
 }
 
-template <int E, bool BACKWARD>
-static int s3rec_train_launch(const S3Train& p, hipStream_t stream) {
-  const size_t lds = s3rec_train_lds_bytes(E, p.enc.L);
-  auto kernel = BACKWARD ? &s3rec_backward_kernel<E> : &s3rec_encode_train_kernel<E>;
-  static bool raised = false;                        // per instantiation, as s3rec_launch
-  if (!raised && lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-    if (e != hipSuccess) return (int)e;
-    raised = true;
-  }
-  const int grid = (int)std::min<int64_t>(p.enc.B, 1 << 20);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, stream, p);
-  return launch_status();
-}
-
-template <bool BACKWARD>
-static int s3rec_train_dispatch(const S3Train& p, int E, void* stream) {
-  switch (E) {
-    case 16: return s3rec_train_launch<16, BACKWARD>(p, (hipStream_t)stream);
-    case 32: return s3rec_train_launch<32, BACKWARD>(p, (hipStream_t)stream);
-    case 64: return s3rec_train_launch<64, BACKWARD>(p, (hipStream_t)stream);
-    default: return s3rec_train_launch<128, BACKWARD>(p, (hipStream_t)stream);
-  }
-}
-
 static int s3rec_train_args(int64_t B, int L, int E, int heads, int blocks, double p, int64_t workspace_floats) {
-  if (B < 0 || L <= 0 || E <= 0 || heads <= 0 || blocks <= 0 || !(p >= 0.0 && p < 1.0)) return YR_ERR_BADARG;
-  if (!s3rec_width_ok(E) || L > kS3MaxL || heads > kS3MaxHeads || blocks > kS3MaxBlocks) return YR_ERR_UNSUPPORTED;
+  if (!(p >= 0.0 && p < 1.0)) return YR_ERR_BADARG;
+  if (const int s = s3rec_shape_status(B, L, E, heads, blocks)) return s;
   if (B > 0 && workspace_floats < blocks * s3_layout(B * L, E, heads).block) return YR_ERR_BADARG;
   return 0;
 }
@@ -1178,7 +993,7 @@ extern "C" int yr_s3rec_encode_train(const float* item_emb, const float* pos_enc
   if (((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(workspace)) & 15) != 0) return YR_ERR_BADARG;
   const S3Train t{S3Enc{item_emb, pos_enc, params, X, B, num_items, L, heads, blocks, 0, out, err_flag}, workspace,
                   nullptr, seed, (float)p, (float)(1.0 / (1.0 - p))};
-  return s3rec_train_dispatch<false>(t, E, stream);
+  return s3rec_encode_launch<true>(t, E, stream);
 }
 
 extern "C" int yr_s3rec_backward(const float* params, const int64_t* X, const float* dh_out, int64_t B, int L, int E,
@@ -1190,7 +1005,7 @@ extern "C" int yr_s3rec_backward(const float* params, const int64_t* X, const fl
   if (((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(workspace)) & 15) != 0) return YR_ERR_BADARG;
   const S3Train t{S3Enc{nullptr, nullptr, params, X, B, 0, L, heads, blocks, 0, d_emb, nullptr}, workspace, dh_out, seed,
                   (float)p, (float)(1.0 / (1.0 - p))};
-  return s3rec_train_dispatch<true>(t, E, stream);
+  return s3rec_backward_launch(t, E, stream);
 }
 
 extern "C" int yr_s3rec_score_grad(const float* item_emb, const int64_t* pos_items, const int64_t* neg_items,
