@@ -48,7 +48,7 @@ BUDGETS = [
     (r"void yr::et_hint_bound_kernel<(256|512|1024)>", 64, 0, "the dot product is a loop: eight waves per SIMD"),
     (r"void yr::adam_dual_wide_kernel<(true|false)>", 64, 1024, "streaming pass, as adam_dual_kernel"),
     # the wide hidden sizes (512 / 1024) of CDAE on list batches
-    (r"void yr::cdae_sampled_decode_wide_kernel<(512|1024), (true|false)>", 128, 34 * 1024,
+    (r"void yr::cdae_sampled_decode_kernel<64, (8|16), true, (true|false)>", 128, 34 * 1024,
      "a wave per position, two W_o rows of 8 / 16 registers in flight beside z and dz: four waves per SIMD "
      "(512 / 4 -> 128) = four workgroups per CU, 4 x 33 KB of 160 KB LDS (staged list 16 KB + 4 x H floats of dz)"),
     (r"void yr::cdae_hidden_bwd_dwh_t_kernel<(2|4)>", 64, 17 * 1024,

@@ -7,6 +7,10 @@ l + 64 k (gradient form) or [4 l + 256 k, 4 l + 256 k + 4) (loss-only form) — 
 the dot product z . W_o[i] while that unit's own outputs (dz[:, h], dW_o[:, h]) stay right.  With
 cdae_ref64.decoder_params one of 1,024 units carries ~0.1 % of a pre-activation, which the bars cannot see; the
 probe inputs below give a few chosen units ~3 % each.
+
+The 32-lane instances of cdae_sampled_decode_kernel (H <= 256) take their slot code from the same kernel text — lane l
+holds floats l + 32 k (gradient form) or [NK l, NK l + NK) (loss-only form), NK = 4 up to H = 128 and 8 above — so the
+NARROW_* cases put the same net under them, at widths with a masked tail (100, 132) and at both exact ones.
 """
 import numpy as np
 
@@ -28,6 +32,11 @@ DWH_CASES = [(512, 1, True), (1024, 0, False), (1024, 1, True)]
 PROBE_DECODE_CASES = [(73, 301, 512, 1, True, False), (40, 301, 1024, 0, True, False), (9, 6001, 1024, 1, True, True),
                       (9, 6001, 512, 0, False, True)]
 PROBE_LOSS_ONLY_CASES = [(15, 6001, 512, 0), (15, 6001, 1024, 1)]
+# the same for the 32-lane instances: NK = 4 (H = 100, 128) and 8 (132, 256); loss only needs H % 4 == 0
+NARROW_PROBE_DECODE_CASES = [(73, 301, 100, 1, True, False), (73, 301, 128, 0, False, False),
+                             (73, 301, 132, 1, True, False), (73, 301, 256, 0, True, False),
+                             (9, 6001, 128, 1, True, True), (9, 6001, 256, 0, False, True)]
+NARROW_PROBE_LOSS_ONLY_CASES = [(15, 6001, 100, 1), (15, 6001, 128, 0), (15, 6001, 256, 1)]
 
 
 def splits_of(B):
@@ -35,10 +44,29 @@ def splits_of(B):
     return max(1, min(8, 512 // B))
 
 
+def narrow_probe_units(H):
+    """probe_units for H <= 256: lanes 0 and 31 of the gradient layout, one unit in every slot h // 32 of it (the last
+    slot may be partial), one at every place h % NK of the loss-only layout (on lanes spread over the half-wave), and
+    the last valid unit H - 1."""
+    NK = 4 if H <= 128 else 8
+    slots = -(-H // 32)
+    units = {0, 31, H - 1}
+    for k in range(slots):
+        units.add(32 * k + (5 * k + 1) % min(32, H - 32 * k))
+    for j in range(NK):
+        units.add(NK * ((3 * j + 2) % (H // NK)) + j)
+    units = np.array(sorted(units), np.int64)
+    assert units.max() == H - 1 and set(units // 32) == set(range(slots))
+    assert set(units % NK) == set(range(NK)) and {0, 31} <= set(units % 32)
+    return units
+
+
 def probe_units(H):
     """Hidden units whose loss from the dot product must be noticed: lanes 0 and 63 of the first and the last register
     slot, both sides of the middle of the row, and one unit in every slot of both lane layouts — slot k = h // 64 of
-    the gradient form, (h // 256, h % 4) of the loss-only form."""
+    the gradient form, (h // 256, h % 4) of the loss-only form.  H <= 256: narrow_probe_units."""
+    if H not in WIDE:
+        return narrow_probe_units(H)
     units = {0, 63, 64, H // 2 - 1, H // 2, H - 64, H - 1}
     for k in range(H // 64):
         units.add(64 * k + (5 * k + 1) % 64)          # (5 k + 1) % 4 runs over 0 .. 3 inside every group of 256

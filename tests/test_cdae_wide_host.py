@@ -120,12 +120,15 @@ def test_every_bar_notices_a_faulty_staging_pass_at_the_wide_widths():
 
 
 @pytest.mark.parametrize("case", [c + (True,) for c in W.PROBE_DECODE_CASES] +
-                         [(B, I, H, act, True, True, False) for B, I, H, act in W.PROBE_LOSS_ONLY_CASES])
+                         [(B, I, H, act, True, True, False) for B, I, H, act in W.PROBE_LOSS_ONLY_CASES] +
+                         [c + (True,) for c in W.NARROW_PROBE_DECODE_CASES] +
+                         [(B, I, H, act, True, True, False) for B, I, H, act in W.NARROW_PROBE_LOSS_ONLY_CASES])
 def test_probe_units_make_a_unit_lost_from_the_dot_product_visible(case):
     """One hidden unit left out of z . W_o[i] (a register slot or a lane of the wave-per-position layout) while the
     unit's own outputs are right: on the probe inputs every probed unit crosses a bar — a loss partial of the row, or
     dz of the row at a probe unit — on every row that has a loss position; with cdae_ref64.decoder_params it does
-    not (shown once, at the first case)."""
+    not (shown once, at the first case).  The same at H = 100, 128, 132 and 256 for the half-wave-per-position
+    instances (tests/test_gpu_cdae_probe_units.py), which share the slot code: cdae_wide_cases.narrow_probe_units."""
     B, I, H, act, with_bo, long, grads = case
     splits = W.splits_of(B)
     c = W.probe_decode_case(B, I, H, act, with_bo, long, settle=not grads)

@@ -114,9 +114,10 @@ def _decode_ratios(engine, ref, B, splits, dz, dWo, dbo, partials, count):
 
 @pytest.mark.parametrize("B,I,H,act,with_bo,long", R.DECODE_CASES)
 def test_sampled_decoder_every_split_count_and_long_rows(device, B, I, H, act, with_bo, long):
-    """cdae_sampled_decode_kernel<NK, false> with gradients: splits 8, 8, 7, 6, 5, 4, 3, 2, 1, 1 on short rows, and the
-    multi-pass walk of the long rows at splits 8, 3 and 1; dz, dW_o, db_o, every loss partial, their sum and the
-    spread count.  splits = 1 stores dz: a sentinel in dz on entry changes nothing."""
+    """cdae_sampled_decode_kernel<32, 4 | 8, false, false> (a half-wave per position) with gradients: splits 8, 8, 7,
+    6, 5, 4, 3, 2, 1, 1 on short rows, and the multi-pass walk of the long rows at splits 8, 3 and 1; dz, dW_o, db_o,
+    every loss partial, their sum and the spread count.  splits = 1 stores dz: a sentinel in dz on entry changes
+    nothing."""
     from yelprecommendation_amd import engine
     c = R.decode_case(B, I, H, act, with_bo, long)
     _, splits, dz, dWo, dbo, partials, count = _decode(engine, device, c, B, H, I, act)
@@ -140,10 +141,10 @@ def test_sampled_decoder_refuses_wide_hidden_layers(device):
 
 @pytest.mark.parametrize("B,I,H,act", R.LOSS_ONLY_CASES)
 def test_loss_only_decoder_and_the_loss_finalizers(device, B, I, H, act):
-    """dz = dWo = dbo = None: the LOSS_ONLY kernel (H % 4 == 0) and the generic kernel without gradients (H = 130) on
-    the long rows and on rows of 31 ... 65 positions (the 32-slot settle() hand-off); then cdae_loss_finalize and
-    cdae_loss_finalize_batched (batch_rows = 7 does not divide the rows; run twice on the same buffers; ``arrive``
-    left at zero) against float64 means per batch."""
+    """dz = dWo = dbo = None: the LOSS_ONLY instances of cdae_sampled_decode_kernel (H % 4 == 0) and the gradient
+    instance run without gradient buffers (H = 130) on the long rows and on rows of 31 ... 65 positions (the 32-slot
+    settle() hand-off); then cdae_loss_finalize and cdae_loss_finalize_batched (batch_rows = 7 does not divide the
+    rows; run twice on the same buffers; ``arrive`` left at zero) against float64 means per batch."""
     from yelprecommendation_amd import engine
     c = R.decode_case(B, I, H, act, True, True, settle=True)
     L, splits, _, _, _, partials, count = _decode(engine, device, c, B, H, I, act, grads=False)

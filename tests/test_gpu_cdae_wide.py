@@ -31,9 +31,9 @@ def _decoder_with_gradients(device, c, B, I, H, act, what):
 
 @pytest.mark.parametrize("B,I,H,act,with_bo,long", W.DECODE_CASES)
 def test_wide_decoder_every_split_count_and_long_rows(device, B, I, H, act, with_bo, long):
-    """cdae_sampled_decode_wide_kernel<512 | 1024, false>: splits 8, 7, 2, 1 on short rows and 8, 8, 3, 1 on the long
-    rows (0 ... 6,001 positions, three staging passes); dz, dW_o, db_o, every loss partial, their sum and the spread
-    count.  splits = 1 stores dz: a sentinel in dz on entry changes nothing."""
+    """cdae_sampled_decode_kernel<64, 8 | 16, true, false> (H = 512 | 1,024): splits 8, 7, 2, 1 on short rows and
+    8, 8, 3, 1 on the long rows (0 ... 6,001 positions, three staging passes); dz, dW_o, db_o, every loss partial,
+    their sum and the spread count.  splits = 1 stores dz: a sentinel in dz on entry changes nothing."""
     _decoder_with_gradients(device, R.decode_case(B, I, H, act, with_bo, long), B, I, H, act, "wide decoder")
 
 
@@ -85,9 +85,9 @@ def _loss_only(device, c, B, I, H, act, what):
 
 @pytest.mark.parametrize("B,I,H,act", W.LOSS_ONLY_CASES)
 def test_wide_loss_only_decoder_and_the_loss_finalizers(device, B, I, H, act):
-    """dz = dWo = dbo = None: cdae_sampled_decode_wide_kernel<., true> at 8 splits on the long rows (up to 188 positions
-    per wave and pass: the 64-slot settle() hand-off is passed twice and ends in a partial round) and on rows of
-    31 ... 65 positions (one or two positions per wave, or none); then cdae_loss_finalize and
+    """dz = dWo = dbo = None: cdae_sampled_decode_kernel<64, ., true, true> at 8 splits on the long rows (up to 188
+    positions per wave and pass: the 64-slot settle() hand-off is passed twice and ends in a partial round) and on
+    rows of 31 ... 65 positions (one or two positions per wave, or none); then cdae_loss_finalize and
     cdae_loss_finalize_batched on its partials."""
     _loss_only(device, R.decode_case(B, I, H, act, True, True, settle=True), B, I, H, act, "wide loss only")
 

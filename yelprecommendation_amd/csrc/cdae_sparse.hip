@@ -345,332 +345,200 @@ __global__ __launch_bounds__(kBlock) void cdae_hidden_bwd_dwh_t_kernel(
 // yr_cdae_compact_pair: ONE pass over x and the negative mask makes both lists of a row — the non-zeros of
 //   dropout_p(x) (the encoder's input, as yr_cdae_compact_rows) and the loss positions (column, target):
 //   cdae_compact_rows_kernel<true> above.
-// yr_cdae_sampled_decode: one workgroup per (row, 1 / S of its position list); a HALF-wave per position: lane l
-//   holds floats [4 l, 4 l + 4) of the W_o row (one 512-byte gather per position at H = 128), the dot with z
-//   is a 32-lane DPP sum; then, with the same W_o row still in registers,
+// yr_cdae_sampled_decode: one workgroup per (row, 1 / S of its position list); a group of LPP lanes per position,
+//   every lane holding EPL floats of the W_o row; the dot with z is an LPP-lane DPP sum; then, with the same W_o
+//   row still in registers,
 //     y = act(z . W_o[i] + b_o[i]);  BCE term -> the workgroup's loss partial (fixed order);
 //     g = (y - t) / max((1 - y) y, 1e-12) * act'(y)            (without 1 / count: the consumers scale)
-//     dz[b, :]   += g W_o[i, :]        registers, combined over the half-waves in fixed order
-//     dW_o[i, :] += g z[b, :]          float atomics, 512 contiguous bytes per position
+//     dz[b, :]   += g W_o[i, :]        registers, combined over the lane groups in fixed order
+//     dW_o[i, :] += g z[b, :]          float atomics, contiguous bytes per position
 //     db_o[i]    += g
 //   count (spread, see YR_COUNT_SLOTS) += positions.  dW_o / db_o must be zero where no earlier position of
-//   this step wrote; dz zero on entry when S > 1.  H <= 256; H = 512 and 1,024 take the wave-per-position form
-//   further down (cdae_sampled_decode_wide_kernel).
-constexpr int kHalf = 32;
-constexpr int kHalves = kBlock / kHalf;
+//   this step wrote; dz zero on entry when S > 1.
+// One kernel text, cdae_sampled_decode_kernel<LPP, EPL, EXACT, LOSS_ONLY>, in two geometries (DecodeGeom):
+//   H <= 256        a HALF-wave per position (LPP = 32; EPL = 4 up to H = 128, 8 above), H at run time: the slots
+//                   past H are masked and their loads clamped into the row;
+//   H = 512, 1,024  a whole WAVE per position (LPP = 64; EPL = 8, 16), H = LPP x EPL at compile time, no masks.  In
+//                   the half-wave layout a lane would hold 4 x 32 row registers at H = 1,024 (z, dz, two W_o rows in
+//                   flight) and s_dz would take 32 KB; here s_dz is 4 x H floats.
+// and two lane layouts:
+//   with gradients  lane l holds floats l + LPP k of a row, so that every load / atomic instruction of a group
+//                   covers 4 LPP contiguous bytes (128 or 256: the shape the float atomics run at full rate for);
+//   LOSS_ONLY       (validation: NULL gradient buffers, H % 4 == 0) 16-byte loads: lane l holds [EPL l, EPL l + EPL)
+//                   at 32 lanes (one load per lane and position at H = 128) and [4 l + 256 k, 4 l + 256 k + 4) at 64
+//                   (1 KB per wave instruction) — not the same rule.  The BCE term of a position is computed ONCE, by
+//                   the lane whose number is the position's place in its run of LPP — the exponential and the two
+//                   logarithms were 60 % of the instructions when every lane of the half-wave computed them (82 ->
+//                   45 us per 4,096 rows) — and no s_dz is allocated.
+template <int LPP, int EPL, bool EXACT, bool LOSS_ONLY>
+struct DecodeGeom {
+  static_assert((LPP == 32 && (EPL == 4 || EPL == 8)) || (LPP == kWave && (EPL == 8 || EPL == 16)), "lanes x floats per lane");
+  static constexpr int kRow = LPP * EPL;            // the floats a lane group covers; H itself when EXACT
+  static constexpr int kVec = LOSS_ONLY ? 4 : 1;    // floats per load instruction
+  // float index of slot k of a lane
+  static __device__ __forceinline__ int at(int lane, int k) {
+    if constexpr (!LOSS_ONLY) return lane + LPP * k;
+    else if constexpr (LPP == 32) return EPL * lane + k;
+    else return 4 * lane + 4 * LPP * (k / 4) + k % 4;
+  }
+  static __device__ __forceinline__ bool in(int lane, int k, int H) { return EXACT || at(lane, k) < H; }
+  // a lane's slots of a row; past H the load is clamped into the row (rows are 16-byte aligned and H % 4 == 0 in the
+  // LOSS_ONLY layout: checked by the entry point) and the mask drops what it fetched
+  static __device__ __forceinline__ void load(const float* __restrict__ row, int lane, int H, float (&v)[EPL]) {
+#pragma unroll
+    for (int k = 0; k < EPL; k += kVec) {
+      const int q = EXACT ? at(lane, k) : min(at(lane, k), H - kVec);
+      if constexpr (LOSS_ONLY) {
+        const float4 f = ld4(row + q);
+        v[k] = f.x; v[k + 1] = f.y; v[k + 2] = f.z; v[k + 3] = f.w;
+      } else {
+        v[k] = row[q];
+      }
+    }
+  }
+  // this lane's part of w . z: slot after slot with gradients, a 16-byte load's four products first in LOSS_ONLY
+  static __device__ __forceinline__ float dot(const float (&w)[EPL], const float (&zr)[EPL], const bool (&in)[EPL]) {
+    float d = 0.0f;
+#pragma unroll
+    for (int k = 0; k < EPL; k += kVec) {
+      if constexpr (LOSS_ONLY)
+        d += (in[k] ? w[k] * zr[k] : 0.0f) + (in[k + 1] ? w[k + 1] * zr[k + 1] : 0.0f) +
+             (in[k + 2] ? w[k + 2] * zr[k + 2] : 0.0f) + (in[k + 3] ? w[k + 3] * zr[k + 3] : 0.0f);
+      else
+        d += in[k] ? w[k] * zr[k] : 0.0f;
+    }
+    return d;
+  }
+};
 
-// LOSS_ONLY (validation: NULL gradient buffers): lane l holds floats [NK l, NK l + NK) of a row (one 16-byte load per
-// lane and position at H = 128), and the BCE term of a position is computed ONCE, by the lane whose number is the
-// position's place in its group of 32 — the exponential and the two logarithms were 60 % of the instructions when
-// every lane of the half-wave computed them (82 -> 45 us per 4,096 rows).
-template <int NK, bool LOSS_ONLY>   // H <= 32 * NK: lane l of a half-wave holds floats l, l + 32, ... of a row, so that every
-                        // load / atomic instruction of a half-wave covers 128 contiguous bytes
+__device__ __forceinline__ float decode_output(float pre, int act) {
+  return act == 1 ? 1.0f / (1.0f + expf(-pre)) : pre;
+}
+
+// the BCE term of a prediction y for target t (logarithms clamped at -100 as torch's BCELoss), and its gradient
+// w.r.t. the pre-activation
+__device__ __forceinline__ float bce_term(float y, float t) {
+  return -(t * fmaxf(logf(y), -100.0f) + (1.0f - t) * fmaxf(logf(1.0f - y), -100.0f));
+}
+
+__device__ __forceinline__ float bce_grad(float y, float t, int act) {
+  float g = (y - t) / fmaxf((1.0f - y) * y, 1e-12f);
+  if (act == 1) g *= y * (1.0f - y);
+  return g;
+}
+
+template <int LPP, int EPL, bool EXACT, bool LOSS_ONLY>
 __global__ __launch_bounds__(kBlock) void cdae_sampled_decode_kernel(
     const int32_t* __restrict__ lcols, const float* __restrict__ lvals, const int32_t* __restrict__ lcount,
-    int64_t cpp, const float* __restrict__ z, const float* __restrict__ Wo, const float* __restrict__ bo, int H,
+    int64_t cpp, const float* __restrict__ z, const float* __restrict__ Wo, const float* __restrict__ bo, int H_arg,
     int act, int splits, float* __restrict__ dz, float* __restrict__ dWo, float* __restrict__ dbo,
     float* __restrict__ partial_loss, int32_t* __restrict__ count) {
+  using G = DecodeGeom<LPP, EPL, EXACT, LOSS_ONLY>;
+  constexpr int kGroups = kBlock / LPP;             // positions a workgroup works on at a time
   __shared__ int s_pre[kListParts + 1];
   __shared__ int32_t s_col[kListCap];
   __shared__ float s_val[kListCap];
-  __shared__ float s_dz[kHalves][kHalf * NK];
-  __shared__ float s_loss[kHalves];
-  __shared__ int s_done[kHalves];
+  __shared__ float s_dz[LOSS_ONLY ? 1 : kGroups][LOSS_ONLY ? 1 : G::kRow];
+  __shared__ float s_loss[kGroups];
+  __shared__ int s_done[kGroups];
+  const int H = EXACT ? G::kRow : H_arg;
   const int64_t r = blockIdx.x;
   const int split = blockIdx.y;
-  const int lane = threadIdx.x & (kHalf - 1), half = threadIdx.x / kHalf;
-  float zr[NK], acc[NK];
-  bool in[NK];
+  const int lane = threadIdx.x & (LPP - 1), group = threadIdx.x / LPP;
+  // NULL gradient buffers: the loss only (validation).  An exact width is a multiple of 4, so without gradients it
+  // takes the LOSS_ONLY instance; H = 130 without them runs this one with grads == false
+  const bool grads = !LOSS_ONLY && (EXACT || dWo != nullptr);
+  float zr[EPL], acc[EPL];
+  bool in[EPL];
+  G::load(z + r * H, lane, H, zr);
 #pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    in[k] = lane + kHalf * k < H;
-    zr[k] = in[k] ? z[r * H + lane + kHalf * k] : 0.0f;
+  for (int k = 0; k < EPL; ++k) {
+    in[k] = G::in(lane, k, H);
+    if (!in[k]) zr[k] = 0.0f;
     acc[k] = 0.0f;
   }
   float loss = 0.0f;
   int done = 0;
-  const bool grads = !LOSS_ONLY && dWo != nullptr;   // NULL gradient buffers: the loss only (validation)
-  if constexpr (LOSS_ONLY) {
-    static_assert(NK == 4 || NK == 8, "16-byte loads");
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {                  // this form's layout of z
-      in[k] = NK * lane + k < H;
-      zr[k] = in[k] ? z[r * H + NK * lane + k] : 0.0f;
-    }
-  }
   for (int skip = 0;; skip += kListCap) {
     const int n = gather_row_list(lcols, lvals, lcount, cpp, r, skip, s_pre, s_col, s_val);
-    if constexpr (LOSS_ONLY) {
-      float pre_mine = 0.0f, t_mine = 0.0f;
-      bool have = false;
-      int slot = 0;
-      auto settle = [&]() {                         // every lane: the BCE term of the position it was handed
-        if (have) {
-          float y = pre_mine;
-          if (act == 1) y = 1.0f / (1.0f + expf(-y));
-          loss -= t_mine * fmaxf(logf(y), -100.0f) + (1.0f - t_mine) * fmaxf(logf(1.0f - y), -100.0f);
-        }
-        have = false;
-        slot = 0;
-      };
-      for (int j0 = split + half * splits; j0 < n; j0 += 2 * kHalves * splits) {
-        const int j1 = j0 + kHalves * splits;
-        const bool two = j1 < n;
-        const int col0 = s_col[j0], col1 = s_col[two ? j1 : j0];
-        float4 w0[NK / 4], w1[NK / 4];
-#pragma unroll
-        for (int k = 0; k < NK / 4; ++k) {          // (rows are 16-byte aligned: H % 4 == 0 checked by the entry point)
-          const int q = min(NK * lane + 4 * k, H - 4);
-          w0[k] = *reinterpret_cast<const float4*>(Wo + (int64_t)col0 * H + q);
-          w1[k] = *reinterpret_cast<const float4*>(Wo + (int64_t)col1 * H + q);
-        }
-        const float b0 = bo ? bo[col0] : 0.0f, b1 = bo ? bo[col1] : 0.0f;
-#pragma unroll
-        for (int which = 0; which < 2; ++which) {
-          if (which == 1 && !two) break;
-          float d = 0.0f;
-#pragma unroll
-          for (int k = 0; k < NK / 4; ++k) {
-            const float4 w = which ? w1[k] : w0[k];
-            d += (in[4 * k] ? w.x * zr[4 * k] : 0.0f) + (in[4 * k + 1] ? w.y * zr[4 * k + 1] : 0.0f) +
-                 (in[4 * k + 2] ? w.z * zr[4 * k + 2] : 0.0f) + (in[4 * k + 3] ? w.w * zr[4 * k + 3] : 0.0f);
-          }
-          d = group_sum_dpp<kHalf>(d);
-          if (lane == slot) {
-            pre_mine = d + (which ? b1 : b0);
-            t_mine = s_val[which ? j1 : j0];
-            have = true;
-          }
-          ++done;
-          if (++slot == kHalf) settle();
-        }
-      }
-      settle();
-    } else
-
-    // this workgroup's share of the staged entries: j = split, split + splits, ...; half-wave `half` takes every
-    // kHalves-th of those, two at a time (the second W_o row is in flight while the first is used)
-    for (int j0 = split + half * splits; j0 < n; j0 += 2 * kHalves * splits) {
-      const int j1 = j0 + kHalves * splits;
+    // LOSS_ONLY: the (pre-activation, target) this lane was handed, and how many lanes of its group hold one
+    float pre_mine = 0.0f, t_mine = 0.0f;
+    bool have = false;
+    int slot = 0;
+    auto settle = [&]() {                           // every lane: the BCE term of the position it was handed
+      if (have) loss += bce_term(decode_output(pre_mine, act), t_mine);
+      have = false;
+      slot = 0;
+    };
+    // this workgroup's share of the staged entries: j = split, split + splits, ...; lane group `group` takes every
+    // kGroups-th of those, two at a time (the second W_o row is in flight while the first is used)
+    for (int j0 = split + group * splits; j0 < n; j0 += 2 * kGroups * splits) {
+      const int j1 = j0 + kGroups * splits;
       const bool two = j1 < n;
       const int col0 = s_col[j0], col1 = s_col[two ? j1 : j0];
-      float w0[NK], w1[NK];
-#pragma unroll
-      for (int k = 0; k < NK; ++k) {
-        const int q = min(lane + kHalf * k, H - 1);
-        w0[k] = Wo[(int64_t)col0 * H + q];
-        w1[k] = Wo[(int64_t)col1 * H + q];
-      }
+      float w0[EPL], w1[EPL];
+      G::load(Wo + (int64_t)col0 * H, lane, H, w0);
+      G::load(Wo + (int64_t)col1 * H, lane, H, w1);
       const float b0 = bo ? bo[col0] : 0.0f, b1 = bo ? bo[col1] : 0.0f;
 #pragma unroll
       for (int which = 0; which < 2; ++which) {
         if (which == 1 && !two) break;
-        const int col = which ? col1 : col0;
-        const float t = s_val[which ? j1 : j0];
-        float d = 0.0f;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) d += in[k] ? (which ? w1[k] : w0[k]) * zr[k] : 0.0f;
-        d = group_sum_dpp<kHalf>(d);
-        float y = d + (which ? b1 : b0);
-        if (act == 1) y = 1.0f / (1.0f + expf(-y));
-        loss -= t * fmaxf(logf(y), -100.0f) + (1.0f - t) * fmaxf(logf(1.0f - y), -100.0f);
-        float g = (y - t) / fmaxf((1.0f - y) * y, 1e-12f);
-        if (act == 1) g *= y * (1.0f - y);
+        const float (&w)[EPL] = which ? w1 : w0;
+        const int j = which ? j1 : j0;
+        const float pre = group_sum_dpp<LPP>(G::dot(w, zr, in)) + (which ? b1 : b0);
         ++done;
-        if (grads) {
-#pragma unroll
-          for (int k = 0; k < NK; ++k) {
-            acc[k] += g * (which ? w1[k] : w0[k]);
-            if (in[k]) atomicAdd(dWo + (int64_t)col * H + lane + kHalf * k, g * zr[k]);
-          }
-          if (lane == 0) atomicAdd(dbo + col, g);
-        }
-      }
-    }
-    const bool more = skip + n < s_pre[kListParts];
-    __syncthreads();
-    if (!more) break;
-  }
-  // combine the half-waves in fixed order
-#pragma unroll
-  for (int k = 0; k < NK; ++k) s_dz[half][lane + kHalf * k] = acc[k];
-  if constexpr (LOSS_ONLY) loss = group_sum_dpp<kHalf>(loss);     // the lanes' own positions, fixed order
-  if (lane == 0) { s_loss[half] = loss; s_done[half] = done; }
-  __syncthreads();
-  for (int h = threadIdx.x; grads && h < H; h += kBlock) {
-    float tsum = 0.0f;
-#pragma unroll
-    for (int k = 0; k < kHalves; ++k) tsum += s_dz[k][h];
-    if (splits > 1) atomicAdd(dz + r * H + h, tsum);
-    else dz[r * H + h] = tsum;
-  }
-  if (threadIdx.x == 0) {
-    float tl = 0.0f;
-    int tot = 0;
-#pragma unroll
-    for (int k = 0; k < kHalves; ++k) { tl += s_loss[k]; tot += s_done[k]; }
-    partial_loss[r * splits + split] = tl;
-    spread_count_add(count, blockIdx.y * gridDim.x + blockIdx.x, tot);
-  }
-}
-
-// The wide form (H = 512 and 1,024): a whole WAVE per position.  In the half-wave layout a lane would hold 4 x 32 row
-// registers at H = 1,024 (z, dz, two W_o rows in flight) and s_dz would take 32 KB.  Here lane l holds floats
-// l + 64 k, k < HW / 64 (RowGeom<HW> of csrc/bpr_mf.hip): every load and every float atomic of a wave covers 256
-// contiguous bytes, the dot product is one 64-lane DPP sum, s_dz is 4 x HW floats.  Everything else is the narrow
-// form: the list staged in passes of kListCap, the splits of a row interleaved over the staged entries, two positions
-// per wave in flight, the waves combined in fixed order, dz stored at splits == 1 and added otherwise.
-// LOSS_ONLY: lane l holds floats [4 l + 256 k, 4 l + 256 k + 4) (16-byte loads, 1 KB per wave instruction), and a
-// position's BCE term is computed once, by the lane whose number is the position's place in its group of 64.
-__device__ __forceinline__ float wave_sum_dpp(float x) {
-  x = group_sum_dpp<32>(x);
-  return x + __shfl_xor(x, 32, kWave);
-}
-
-template <int HW, bool LOSS_ONLY>
-__global__ __launch_bounds__(kBlock) void cdae_sampled_decode_wide_kernel(
-    const int32_t* __restrict__ lcols, const float* __restrict__ lvals, const int32_t* __restrict__ lcount,
-    int64_t cpp, const float* __restrict__ z, const float* __restrict__ Wo, const float* __restrict__ bo, int act,
-    int splits, float* __restrict__ dz, float* __restrict__ dWo, float* __restrict__ dbo,
-    float* __restrict__ partial_loss, int32_t* __restrict__ count) {
-  static_assert(HW == 512 || HW == 1024, "wide hidden sizes");
-  constexpr int EPL = RowGeom<HW>::EPL;              // floats of a row per lane: 8 or 16
-  constexpr int kW = kWavesPerBlock;
-  __shared__ int s_pre[kListParts + 1];
-  __shared__ int32_t s_col[kListCap];
-  __shared__ float s_val[kListCap];
-  __shared__ float s_dz[LOSS_ONLY ? 1 : kW][LOSS_ONLY ? 1 : HW];
-  __shared__ float s_loss[kW];
-  __shared__ int s_done[kW];
-  const int64_t r = blockIdx.x;
-  const int split = blockIdx.y;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  float loss = 0.0f;
-  int done = 0;
-  if constexpr (LOSS_ONLY) {
-    float4 zr[EPL / 4];
-#pragma unroll
-    for (int k = 0; k < EPL / 4; ++k) zr[k] = ld4(z + r * HW + 4 * lane + 4 * kWave * k);
-    for (int skip = 0;; skip += kListCap) {
-      const int n = gather_row_list(lcols, lvals, lcount, cpp, r, skip, s_pre, s_col, s_val);
-      float pre_mine = 0.0f, t_mine = 0.0f;
-      bool have = false;
-      int slot = 0;
-      auto settle = [&]() {                           // every lane: the BCE term of the position it was handed
-        if (have) {
-          float y = pre_mine;
-          if (act == 1) y = 1.0f / (1.0f + expf(-y));
-          loss -= t_mine * fmaxf(logf(y), -100.0f) + (1.0f - t_mine) * fmaxf(logf(1.0f - y), -100.0f);
-        }
-        have = false;
-        slot = 0;
-      };
-      for (int j0 = split + wave * splits; j0 < n; j0 += 2 * kW * splits) {
-        const int j1 = j0 + kW * splits;
-        const bool two = j1 < n;
-        const int col0 = s_col[j0], col1 = s_col[two ? j1 : j0];
-        float4 w0[EPL / 4], w1[EPL / 4];
-#pragma unroll
-        for (int k = 0; k < EPL / 4; ++k) {
-          w0[k] = ld4(Wo + (int64_t)col0 * HW + 4 * lane + 4 * kWave * k);
-          w1[k] = ld4(Wo + (int64_t)col1 * HW + 4 * lane + 4 * kWave * k);
-        }
-        const float b0 = bo ? bo[col0] : 0.0f, b1 = bo ? bo[col1] : 0.0f;
-#pragma unroll
-        for (int which = 0; which < 2; ++which) {
-          if (which == 1 && !two) break;
-          float d = 0.0f;
-#pragma unroll
-          for (int k = 0; k < EPL / 4; ++k) {
-            const float4 w = which ? w1[k] : w0[k];
-            d += w.x * zr[k].x + w.y * zr[k].y + w.z * zr[k].z + w.w * zr[k].w;
-          }
-          d = wave_sum_dpp(d);
+        if constexpr (LOSS_ONLY) {
           if (lane == slot) {
-            pre_mine = d + (which ? b1 : b0);
-            t_mine = s_val[which ? j1 : j0];
+            pre_mine = pre;
+            t_mine = s_val[j];
             have = true;
           }
-          ++done;
-          if (++slot == kWave) settle();
-        }
-      }
-      settle();
-      const bool more = skip + n < s_pre[kListParts];
-      __syncthreads();
-      if (!more) break;
-    }
-    loss = wave_sum_dpp(loss);                        // the lanes' own positions, fixed order
-  } else {
-    float zr[EPL], acc[EPL];
-#pragma unroll
-    for (int k = 0; k < EPL; ++k) {
-      zr[k] = z[r * HW + lane + kWave * k];
-      acc[k] = 0.0f;
-    }
-    for (int skip = 0;; skip += kListCap) {
-      const int n = gather_row_list(lcols, lvals, lcount, cpp, r, skip, s_pre, s_col, s_val);
-      // this workgroup's share of the staged entries: j = split, split + splits, ...; wave `wave` takes every kW-th of
-      // those, two at a time (the second W_o row is in flight while the first is used)
-      for (int j0 = split + wave * splits; j0 < n; j0 += 2 * kW * splits) {
-        const int j1 = j0 + kW * splits;
-        const bool two = j1 < n;
-        const int col0 = s_col[j0], col1 = s_col[two ? j1 : j0];
-        float w0[EPL], w1[EPL];
-#pragma unroll
-        for (int k = 0; k < EPL; ++k) {
-          w0[k] = Wo[(int64_t)col0 * HW + lane + kWave * k];
-          w1[k] = Wo[(int64_t)col1 * HW + lane + kWave * k];
-        }
-        const float b0 = bo ? bo[col0] : 0.0f, b1 = bo ? bo[col1] : 0.0f;
-#pragma unroll
-        for (int which = 0; which < 2; ++which) {
-          if (which == 1 && !two) break;
+          if (++slot == LPP) settle();
+        } else {
           const int col = which ? col1 : col0;
-          const float t = s_val[which ? j1 : j0];
-          float d = 0.0f;
+          const float t = s_val[j];
+          const float y = decode_output(pre, act);
+          loss += bce_term(y, t);
+          const float g = bce_grad(y, t, act);
+          if (grads) {
 #pragma unroll
-          for (int k = 0; k < EPL; ++k) d += (which ? w1[k] : w0[k]) * zr[k];
-          d = wave_sum_dpp(d);
-          float y = d + (which ? b1 : b0);
-          if (act == 1) y = 1.0f / (1.0f + expf(-y));
-          loss -= t * fmaxf(logf(y), -100.0f) + (1.0f - t) * fmaxf(logf(1.0f - y), -100.0f);
-          float g = (y - t) / fmaxf((1.0f - y) * y, 1e-12f);
-          if (act == 1) g *= y * (1.0f - y);
-          ++done;
-          float* grow = dWo + (int64_t)col * HW + lane;
-#pragma unroll
-          for (int k = 0; k < EPL; ++k) {
-            acc[k] += g * (which ? w1[k] : w0[k]);
-            atomicAdd(grow + kWave * k, g * zr[k]);
+            for (int k = 0; k < EPL; ++k) {
+              acc[k] += g * w[k];
+              if (in[k]) atomicAdd(dWo + (int64_t)col * H + G::at(lane, k), g * zr[k]);
+            }
+            if (lane == 0) atomicAdd(dbo + col, g);
           }
-          if (lane == 0) atomicAdd(dbo + col, g);
         }
       }
-      const bool more = skip + n < s_pre[kListParts];
-      __syncthreads();
-      if (!more) break;
     }
-#pragma unroll
-    for (int k = 0; k < EPL; ++k) s_dz[wave][lane + kWave * k] = acc[k];
+    if constexpr (LOSS_ONLY) settle();
+    const bool more = skip + n < s_pre[kListParts];
+    __syncthreads();                                // the staged list is overwritten by the next pass
+    if (!more) break;
   }
-  // combine the waves in fixed order
-  if (lane == 0) { s_loss[wave] = loss; s_done[wave] = done; }
+  // combine the lane groups in fixed order
+  if constexpr (LOSS_ONLY) {
+    loss = group_sum_dpp<LPP>(loss);                // the lanes' own positions, fixed order
+  } else {
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) s_dz[group][G::at(lane, k)] = acc[k];
+  }
+  if (lane == 0) { s_loss[group] = loss; s_done[group] = done; }
   __syncthreads();
   if constexpr (!LOSS_ONLY) {
-    for (int h = threadIdx.x; h < HW; h += kBlock) {
+    for (int h = threadIdx.x; grads && h < H; h += kBlock) {
       float tsum = 0.0f;
 #pragma unroll
-      for (int k = 0; k < kW; ++k) tsum += s_dz[k][h];
-      if (splits > 1) atomicAdd(dz + r * HW + h, tsum);
-      else dz[r * HW + h] = tsum;
+      for (int k = 0; k < kGroups; ++k) tsum += s_dz[k][h];
+      if (splits > 1) atomicAdd(dz + r * H + h, tsum);
+      else dz[r * H + h] = tsum;
     }
   }
   if (threadIdx.x == 0) {
     float tl = 0.0f;
     int tot = 0;
 #pragma unroll
-    for (int k = 0; k < kW; ++k) { tl += s_loss[k]; tot += s_done[k]; }
+    for (int k = 0; k < kGroups; ++k) { tl += s_loss[k]; tot += s_done[k]; }
     partial_loss[r * splits + split] = tl;
     spread_count_add(count, blockIdx.y * gridDim.x + blockIdx.x, tot);
   }
@@ -850,17 +718,13 @@ extern "C" int yr_cdae_sampled_decode(const int32_t* loss_cols, const float* los
   const dim3 grid((unsigned)B, (unsigned)splits);
   hipStream_t s = (hipStream_t)stream;
   const bool loss_only = !dWo && H % 4 == 0;
-#define YR_SD(NK, LO)                                                                                                 \
-  hipLaunchKernelGGL((cdae_sampled_decode_kernel<NK, LO>), grid, dim3(kBlock), 0, s, loss_cols, loss_targets, loss_count, \
-                     cpp, z, Wo, bo, H, act, splits, dz, dWo, dbo, partial_loss, count)
-#define YR_SDW(HW, LO)                                                                                                \
-  hipLaunchKernelGGL((cdae_sampled_decode_wide_kernel<HW, LO>), grid, dim3(kBlock), 0, s, loss_cols, loss_targets,    \
-                     loss_count, cpp, z, Wo, bo, act, splits, dz, dWo, dbo, partial_loss, count)
-  if (H <= 128) { if (loss_only) YR_SD(4, true); else YR_SD(4, false); }
-  else if (H <= 256) { if (loss_only) YR_SD(8, true); else YR_SD(8, false); }
-  else if (H == 512) { if (loss_only) YR_SDW(512, true); else YR_SDW(512, false); }
-  else { if (loss_only) YR_SDW(1024, true); else YR_SDW(1024, false); }
-#undef YR_SDW
+#define YR_SD(LPP, EPL, EXACT, LO)                                                                                    \
+  hipLaunchKernelGGL((cdae_sampled_decode_kernel<LPP, EPL, EXACT, LO>), grid, dim3(kBlock), 0, s, loss_cols,          \
+                     loss_targets, loss_count, cpp, z, Wo, bo, H, act, splits, dz, dWo, dbo, partial_loss, count)
+  if (H <= 128) { if (loss_only) YR_SD(32, 4, false, true); else YR_SD(32, 4, false, false); }
+  else if (H <= 256) { if (loss_only) YR_SD(32, 8, false, true); else YR_SD(32, 8, false, false); }
+  else if (H == 512) { if (loss_only) YR_SD(64, 8, true, true); else YR_SD(64, 8, true, false); }
+  else { if (loss_only) YR_SD(64, 16, true, true); else YR_SD(64, 16, true, false); }
 #undef YR_SD
   return launch_status();
 }

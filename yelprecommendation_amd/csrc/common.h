@@ -50,15 +50,16 @@ __device__ __forceinline__ float dpp_add(float x) {
 }
 
 // Sum over aligned groups of LPR lanes using DPP (no LDS crossbar traffic): quad swaps, then the
-// mirror forms inside a 16-lane DPP row; 32-lane groups add one cross-row shuffle.
+// mirror forms inside a 16-lane DPP row; 32-lane groups add one cross-row shuffle, the whole wave a second one.
 template <int LPR>
 __device__ __forceinline__ float group_sum_dpp(float x) {
-  static_assert(LPR == 4 || LPR == 8 || LPR == 16 || LPR == 32, "group size");
+  static_assert(LPR == 4 || LPR == 8 || LPR == 16 || LPR == 32 || LPR == 64, "group size");
   x = dpp_add<0xB1>(x);                      // quad_perm [1,0,3,2]
   x = dpp_add<0x4E>(x);                      // quad_perm [2,3,0,1]
   if (LPR >= 8) x = dpp_add<0x141>(x);       // row_half_mirror
   if (LPR >= 16) x = dpp_add<0x140>(x);      // row_mirror
   if (LPR >= 32) x += __shfl_xor(x, 16, kWave);
+  if (LPR >= 64) x += __shfl_xor(x, 32, kWave);
   return x;
 }
 
