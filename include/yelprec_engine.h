@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YR_ENGINE_VERSION 34
+#define YR_ENGINE_VERSION 35
 
 #define YR_ERR_UNSUPPORTED (-1) /* embedding width / option not compiled in   */
 #define YR_ERR_BADARG      (-2) /* null pointer, negative size, misalignment  */
@@ -883,7 +883,38 @@ int yr_s3rec_item_grad(const int64_t *sorted_ids, const int64_t *order, const fl
                        float *partial, float *d_item, int32_t *err_flag, void *stream);
 
 /* ---------------------------------------------------------------------------
- * Device-side S3Rec sequence batches   (reference data/datasets/s3rec_data_pipeline.py:13-50: split +
+ * S3Rec pre-training: catalogue BCE   (reference trainers/s3rec_trainer.py:137-152 over models/s3rec.py:137-164:
+ *   binary_cross_entropy_with_logits between [B, L, R] logits and a dense [B, L, R] target array, mean over all
+ *   elements; csrc/s3rec_pretrain.hip)
+ * F [N][E] (the projected encoder rows, N = B L) against every row of a table T [R][E] (item_embedding.weight with
+ * R = num_items + 1: MIP; attribute_embedding.weight with R = attributes_count: AAP, MAP), both 16-byte aligned:
+ *     z[n, r] = zscale[n] <F[n], T[r]>          y[n, r] = yscale[n] [r in targets(key[n])]
+ *     row_loss[n] = sum_r ( max(z, 0) - z y + log1p(exp(-|z|)) )          loss = (sum_n row_loss[n]) / (N R)
+ *     g[n, r] = zscale[n] (sigmoid(z) - y) / (N R)          dF [N][E] = g T          dT [R][E] = g^T F
+ * zscale, yscale [N]: the 0.0 / 1.0 factors `masks` / `not masks` put on the logits and on the targets.  key [N]: the
+ * item id of the position; its targets are tgt_idx[tgt_ptr[key] .. tgt_ptr[key + 1]) (a CSR over K keys, ascending
+ * and duplicate-free inside a key, any length), or, with tgt_ptr = tgt_idx = null, the column `key` itself (MIP: the
+ * one-hot row of s3rec_trainer.py:125).  A key outside [0, K) raises YR_FLAG_BAD_ITEM and counts as a row without
+ * targets; a target outside [0, R) is no column.
+ * loss [1] is required; row_loss, dF, dT may each be null (both gradients null: the loss-only call).  dF and dT are
+ * overwritten, not accumulated.  No [N][R] array is written in any pass: the pass that owns rows of F takes the loss
+ * and dF, the pass that owns rows of T computes the logits again for dT.  No float atomics: the column sums of a row
+ * run over chunks of 2,048 columns in a fixed order (a row's row_loss and dF do not depend on N), dT's row sums over
+ * the 32-row tiles dealt to four waves; two calls give one answer bit for bit.  A row with zscale = 0 adds R times
+ * (float) log 2 to row_loss and exactly zero to dF and dT.
+ * workspace: yr_s3rec_catalogue_bce_workspace_floats(N, R, E) floats (a negative YR_ERR_* for refused sizes), any
+ * contents.  Checked before any launch: negative sizes, E <= 0: YR_ERR_BADARG; a width outside 16 / 32 / 64 / 128:
+ * YR_ERR_UNSUPPORTED; then N == 0 or R == 0: 0 (nothing is written); then null or misaligned pointers, one half of
+ * the CSR without the other, a workspace too small: YR_ERR_BADARG.
+ * ------------------------------------------------------------------------- */
+int64_t yr_s3rec_catalogue_bce_workspace_floats(int64_t N, int64_t R, int E);
+int yr_s3rec_catalogue_bce(const float *F, const float *T, const float *zscale, const float *yscale,
+                           const int64_t *key, const int64_t *tgt_ptr, const int64_t *tgt_idx, int64_t N, int64_t R,
+                           int64_t K, int E, float *loss, float *row_loss, float *dF, float *dT, float *workspace,
+                           int64_t workspace_floats, int32_t *err_flag, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Device-side S3Rec sequence batches  (reference data/datasets/s3rec_data_pipeline.py:13-50: split +
  *   _adjust_seq_len; data/datasets/s3rec_dataset.py:21-57: __getitem__ + _negative_sampling)
  * For the B users of `users`, from the per-user behaviour rows beh_ptr [num_users + 1] / beh_idx (raw item ids in
  * [0, num_items), interaction order, repeats allowed) and the per-user avoid values avoid_ptr / avoid_idx (ascending

@@ -67,6 +67,12 @@ BUDGETS = [
      "admits one workgroup per CU, so one wave per SIMD (512 registers) costs nothing there; no scratch"),
     (r"yr::s3rec_(score_grad|item_partials|item_combine)_kernel", 64, 0,
      "element-wise pass and the two ordered passes of the item gradient: eight waves per SIMD"),
+    (r"void yr::s3rec_cbce_kernel<(16|32|64), (true|false)>", 256, 9 * 1024,
+     "S3Rec pre-training, catalogue BCE: the owned rows (E / 2 registers) and their gradient (E / 2) stay in registers "
+     "beside one tile of logits; two workgroups per CU = two waves per SIMD (512 / 2 -> 256)"),
+    (r"void yr::s3rec_cbce_kernel<128, (true|false)>", 512, 17 * 1024,
+     "as above at E = 128: 64 + 64 row registers, one wave per SIMD; 16.1 KB of LDS for the wave-order sum; no scratch"),
+    (r"yr::s3rec_cbce_(reduce|loss)_kernel", 64, 3 * 1024, "streaming sums in a fixed order"),
 ]
 # Scratch (spilled registers) per lane.  The forms the benchmark and the trainers run by default — width 64, summation
 # order free — must have none; the deterministic-order forms and some forms of the other widths are held at 64 VGPRs by

@@ -12,9 +12,10 @@ Two things to know:
 * The reference tests its 1-based draw against the raw 0-based ``behaviors`` list — an off-by-one of its own: the
   value v is refused when the user has the item whose 1-based id is v + 1.  It is kept, here and (by default) on the
   device path, so that both sample from the reference's distribution.
-* ``aap_actual`` / ``mip_actual`` are left out.  Only pre-training reads them (it is not built), ``mip_actual`` alone
-  is ``max_seq_len x (num_items + 1)`` doubles per user, and building them draws no random numbers: leaving them out
-  moves nothing in the RNG stream.
+* ``aap_actual`` / ``mip_actual`` are left out.  Only the reference's pre-training reads them; ``S3RecPreTrainer``
+  takes its targets from ``X`` and an item -> categories CSR instead.  ``mip_actual`` alone is ``max_seq_len x
+  (num_items + 1)`` doubles per user, and building them draws no random numbers: leaving them out moves nothing in the
+  RNG stream.
 
 ``to_sequences(device, max_seq_len)`` hands the same behaviour rows to :class:`...s3rec_batches.S3RecSequences`.
 """

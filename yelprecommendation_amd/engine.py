@@ -1539,6 +1539,59 @@ def s3rec_item_grad(X, pos_items, neg_items, d_emb, h, dpos, dneg, d_item, err_f
     return d_item
 
 
+# ---- S3Rec pre-training (csrc/s3rec_pretrain.hip: the catalogue BCE) ----
+def s3rec_item_grad_one(X, d_emb, d_item, err_flag=None):
+    """d_item [num_items + 1, E] += d_emb rows scattered by X alone: yr_s3rec_item_grad with the two score lists
+    switched off (zero coefficients on lookups of X itself, which add exact zeros in the same fixed order)."""
+    zero = torch.zeros(X.numel(), dtype=torch.float32, device=d_emb.device)
+    return s3rec_item_grad(X, X, X, d_emb, d_emb, zero, zero, d_item, err_flag=err_flag)
+
+
+def s3rec_catalogue_bce_workspace_floats(N, R, E):
+    """Floats of the catalogue-BCE workspace (yr_s3rec_catalogue_bce_workspace_floats)."""
+    n = _lib.load().yr_s3rec_catalogue_bce_workspace_floats(N, R, E)
+    if n < 0:
+        check(int(n), "yr_s3rec_catalogue_bce_workspace_floats")
+    return int(n)
+
+
+def s3rec_catalogue_bce(F, T, zscale, yscale, key, tgt_ptr=None, tgt_idx=None, grads=True, want_dF=None, want_dT=None,
+                        workspace=None, err_flag=None):
+    """(loss [1], row_loss [N], dF [N, E] or None, dT [R, E] or None) of yr_s3rec_catalogue_bce: the BCE-with-logits
+    mean over all N R elements of z = zscale <F, T> against y = yscale [r in targets(key)], the targets a CSR over the
+    keys (``tgt_ptr`` [K + 1], ``tgt_idx``, int64) or, without one, the key's own column.  ``grads`` False is the
+    loss-only call; ``want_dF`` / ``want_dT`` pick one gradient."""
+    lib = _lib.load()
+    f32, i64 = torch.float32, torch.int64
+    if F.dim() != 2 or T.dim() != 2 or F.shape[1] != T.shape[1]:
+        raise EngineError(f"s3rec_catalogue_bce: F [N, E] and T [R, E] expected, got {tuple(F.shape)} / {tuple(T.shape)}")
+    (N, E), R = F.shape, T.shape[0]
+    if zscale.numel() != N or yscale.numel() != N or key.numel() != N:
+        raise EngineError("s3rec_catalogue_bce: zscale, yscale and key hold one entry per row of F")
+    if (tgt_ptr is None) != (tgt_idx is None):
+        raise EngineError("s3rec_catalogue_bce: tgt_ptr and tgt_idx come together")
+    K = R if tgt_ptr is None else tgt_ptr.numel() - 1
+    want_dF = grads if want_dF is None else want_dF
+    want_dT = grads if want_dT is None else want_dT
+    dev = F.device
+    if workspace is None:
+        workspace = torch.empty(s3rec_catalogue_bce_workspace_floats(N, R, E), dtype=f32, device=dev)
+    loss = torch.zeros(1, dtype=f32, device=dev)
+    row_loss = torch.zeros(N, dtype=f32, device=dev)
+    dF = torch.empty((N, E), dtype=f32, device=dev) if want_dF else None
+    dT = torch.empty((R, E), dtype=f32, device=dev) if want_dT else None
+    # an empty CSR has no storage to point at: its offsets array stands in (never dereferenced: every list is empty)
+    idx = None if tgt_idx is None else (_dev(tgt_idx, i64, "tgt_idx") if tgt_idx.numel() else _dev(tgt_ptr, i64, "tgt_ptr"))
+    check(lib.yr_s3rec_catalogue_bce(_dev(F, f32, "F"), _dev(T, f32, "T"), _dev(zscale, f32, "zscale"),
+                                     _dev(yscale, f32, "yscale"), _dev(key, i64, "key"), _opt(tgt_ptr, i64, "tgt_ptr"),
+                                     idx, N, R, K, E, loss.data_ptr(), row_loss.data_ptr() if N else None,
+                                     _opt(dF, f32, "dF") if N else None, _opt(dT, f32, "dT") if R else None,
+                                     _dev(workspace, f32, "workspace") if workspace.numel() else None,
+                                     workspace.numel(), _opt(err_flag, torch.int32, "flag"), _stream()),
+          "yr_s3rec_catalogue_bce")
+    return loss, row_loss, dF, dT
+
+
 S3REC_MODES = {"train": 0, "valid": 1, "test": 2}          # YR_S3REC_TRAIN / VALID / TEST
 S3REC_MAX_NEG = 128
 

@@ -20,9 +20,16 @@ model owns, seeded from ``torch.initial_seed()``; ``finetune(..., dropout_seed=s
 scoring: under ``torch.no_grad()`` it scores, with grad enabled it raises NotImplementedError (as it did before training
 was built; ``train()`` mode with ``dropout_ratio = 0`` is training without dropout).
 
-``pretrain`` / ``encode`` raise NotImplementedError — the reference's own ``encode`` calls
-``_self_attention_block`` without its two mask arguments (models/s3rec.py:117-118), so its pre-training cannot run
-as published and there is nothing to be faithful to.
+Pre-training (models/s3rec.py:117-181).  The reference's own ``encode`` calls ``_self_attention_block`` without its
+two mask arguments, so it cannot run as published; the repair is the obvious one: ``encode(X)`` is what ``finetune``
+runs before its prediction layer (``padding_mask = X <= 0`` and the causal mask), every quirk of the encoder kept.
+In ``train()`` mode under grad ``encode`` is an autograd node over the training encoder and the HIP backward; in
+``eval()`` mode under ``torch.no_grad()`` it is the scoring encoder.  ``pretrain(item_masked, segment_masked,
+pos_segments, neg_segments)`` returns the reference's four outputs dense (its ``map()`` uses ``aap_weight``, kept:
+``map_weight`` takes no part and keeps ``grad = None``); the encoding of the segment-masked sequence, which the
+reference computes and never consumes, is skipped.  ``pretrain_loss`` gives the four losses of
+trainers/s3rec_trainer.py:137-158 through the catalogue-BCE kernel (csrc/s3rec_pretrain.hip): no [B, L, num_items +
+1] array exists in its forward or backward.  On CPU tensors all three raise NotImplementedError.
 
 Supported: embed_size 16 / 32 / 64 / 128, max_seq_len 1 .. 64, 1 .. 4 heads, 1 .. 4 blocks; anything else raises
 NotImplementedError at construction.
@@ -224,10 +231,130 @@ class S3Rec(BaseModel):
         return engine.s3rec_candidate_scores(self.item_embedding.weight.detach(), h_last, pos_item.contiguous(),
                                              neg_items.contiguous(), err_flag=self._flag())
 
-    def encode(self, X):
-        raise NotImplementedError("S3Rec.encode: pre-training is not built (the reference's encode() cannot run as "
-                                  "published: models/s3rec.py:117-118)")
+    # -- pre-training (reference models/s3rec.py:117-181) ----------------------------------------------------
+    def _pretrain_on_device(self, what):
+        if not self.item_embedding.weight.is_cuda:
+            raise NotImplementedError(f"S3Rec.{what}: pre-training is not built for CPU tensors (the kernels run on "
+                                      "the GPU only): move the model and the batch to the device")
 
-    def pretrain(self, *sequences):
-        raise NotImplementedError("S3Rec.pretrain: pre-training is not built (the reference's encode() cannot run as "
-                                  "published: models/s3rec.py:117-118)")
+    def encode(self, X, *, dropout_seed=None):
+        """h [B, L, E]: what ``finetune`` runs before its prediction layer (the reference's one-line defect repaired
+        with the masks finetune builds).  eval() under no_grad: the scoring encoder; train() under grad: an autograd
+        node over the training encoder and the HIP backward."""
+        self._pretrain_on_device("encode")
+        if X.dim() != 2 or X.shape[1] != self.cfg.max_seq_len:
+            raise ValueError(f"S3Rec: X must be [batch, max_seq_len = {self.cfg.max_seq_len}], got {tuple(X.shape)}")
+        if torch.is_grad_enabled() and self.training:
+            p = float(self.cfg.dropout_ratio)
+            seed = 0
+            if p > 0.0:
+                seed = self._dropout_seed() if dropout_seed is None else int(dropout_seed)
+            return _EncodeFn.apply(self, X.contiguous(), seed, p, self.item_embedding.weight, self.positional_encoding,
+                                   *self._block_tensors())
+        if torch.is_grad_enabled() or self.training:
+            raise NotImplementedError("S3Rec.encode: pre-training runs in train() mode with grad enabled, scoring in "
+                                      "eval() mode under torch.no_grad()")
+        return self._encode(X, last_only=False)
+
+    def pretrain(self, *sequences, dropout_seeds=None):
+        """reference models/s3rec.py:120-135: (aap [B, L, A], mip [B, L, num_items + 1], map [B, L, A], (sp_pos [B],
+        sp_neg [B])) DENSE, ``encode`` plus ordinary torch products: the reference's surface, the baseline of
+        scripts/bench_s3rec_pretrain.py and the path ``pretrain_loss`` is checked against.  The encoding of the
+        segment-masked sequence, which the reference computes and never consumes, is skipped."""
+        self._pretrain_on_device("pretrain")
+        if len(sequences) != 4:
+            raise TypeError("S3Rec.pretrain(item_masked_sequences, subsequence_masked_sequences, pos_subsequences, "
+                            "neg_subsequences)")
+        item_masked, _segment_masked, pos_segments, neg_segments = sequences
+        s = dropout_seeds or (None, None, None)
+        h = self.encode(item_masked, dropout_seed=s[0])
+        h_pos = self.encode(pos_segments, dropout_seed=s[1])
+        h_neg = self.encode(neg_segments, dropout_seed=s[2])
+        FW = self.aap_weight(h)
+        aap = torch.matmul(FW, self.attribute_embedding.weight.T)
+        mip = torch.matmul(self.mip_weight(h), self.item_embedding.weight.t())
+        map_ = torch.matmul(FW, self.attribute_embedding.weight.T)       # the reference's map() uses aap_weight
+        SW = self.sp_weight(h[:, -1, :])
+        return aap, mip, map_, ((SW * h_pos[:, -1, :]).sum(-1), (SW * h_neg[:, -1, :]).sum(-1))
+
+    def pretrain_loss(self, X, masks, item_masked, pos_segments, neg_segments, attr_ptr, attr_idx, *,
+                      dropout_seeds=None):
+        """(aap_loss, mip_loss, map_loss, sp_loss) of reference trainers/s3rec_trainer.py:137-158 without a
+        [B, L, R] array: X [B, L] the unmasked sequences (the targets come from them), masks [B, L] bool,
+        item_masked = masks * X, the two SP segments, and the device CSR item id -> categories (attr_ptr
+        [num_items + 2], attr_idx; int64).  Each catalogue loss is one autograd node over yr_s3rec_catalogue_bce."""
+        self._pretrain_on_device("pretrain_loss")
+        s = dropout_seeds or (None, None, None)
+        h = self.encode(item_masked, dropout_seed=s[0])
+        h_pos = self.encode(pos_segments, dropout_seed=s[1])
+        h_neg = self.encode(neg_segments, dropout_seed=s[2])
+        B, L, E = h.shape
+        on = masks.reshape(-1).to(torch.float32)
+        off = 1.0 - on
+        ones = torch.ones_like(on)
+        key = X.reshape(-1).contiguous()
+        flag = self._flag()
+        FA = self.aap_weight(h).reshape(B * L, E)
+        FM = self.mip_weight(h).reshape(B * L, E)
+        A, I = self.attribute_embedding.weight, self.item_embedding.weight
+        aap_loss = _CatalogueBCEFn.apply(FA, A, ones, on, key, attr_ptr, attr_idx, flag)
+        mip_loss = _CatalogueBCEFn.apply(FM, I, off, off, key, None, None, flag)
+        map_loss = _CatalogueBCEFn.apply(FA, A, off, off, key, attr_ptr, attr_idx, flag)
+        SW = self.sp_weight(h[:, -1, :])
+        sp_out = torch.cat([(SW * h_neg[:, -1, :]).sum(-1), (SW * h_pos[:, -1, :]).sum(-1)])
+        sp_actual = torch.cat([torch.zeros(B, device=h.device), torch.ones(B, device=h.device)])
+        sp_loss = nn.functional.binary_cross_entropy_with_logits(sp_out, sp_actual)
+        return aap_loss, mip_loss, map_loss, sp_loss
+
+
+class _EncodeFn(torch.autograd.Function):
+    """``encode`` under grad: the stash-keeping encoder forward; backward runs the backward kernel, the gradient
+    products / column sums and the item-lookup gradient of X alone, all in a fixed order without atomics."""
+
+    @staticmethod
+    def forward(ctx, model, X, seed, p, item_emb, pos_enc, *block_tensors):
+        heads, blocks = int(model.cfg.num_heads), int(model.cfg.num_blocks)
+        params = model._params()
+        flag = model._flag()
+        h, ws = engine.s3rec_encode_train(item_emb.detach(), pos_enc.detach(), params, X, heads, blocks, seed=seed, p=p,
+                                          err_flag=flag)
+        ctx.save_for_backward(X, ws, params, item_emb)
+        ctx.cfg = (heads, blocks, seed, p, flag, [t.shape for t in block_tensors])
+        return h
+
+    @staticmethod
+    def backward(ctx, gh):
+        X, ws, params, item_emb = ctx.saved_tensors
+        heads, blocks, seed, p, flag, shapes = ctx.cfg
+        (B, L), E = X.shape, gh.shape[-1]
+        d_emb = engine.s3rec_backward(params, X, gh.contiguous().view(B, L, E), ws, heads, blocks, seed=seed, p=p)
+        packed = engine.s3rec_param_grads(ws, B, L, E, heads, blocks)
+        d_pos = engine.colsum(d_emb.view(B, L * E)).view(L, E)
+        d_item = torch.zeros_like(item_emb)
+        engine.s3rec_item_grad_one(X, d_emb, d_item, err_flag=flag)
+        grads, at = [], 0
+        for shape in shapes:
+            n = shape.numel()
+            grads.append(packed[at:at + n].view(shape))
+            at += n
+        return (None, None, None, None, d_item, d_pos, *grads)
+
+
+class _CatalogueBCEFn(torch.autograd.Function):
+    """One catalogue loss (csrc/s3rec_pretrain.hip): the mean BCE with logits of zscale <F, T> against the listed
+    targets.  The forward call takes the loss and both gradients (the sweep is the cost; the gradient of a scalar
+    needs no second sweep); backward scales them by the arriving gradient."""
+
+    @staticmethod
+    def forward(ctx, F, T, zscale, yscale, key, tgt_ptr, tgt_idx, flag):
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        loss, _, dF, dT = engine.s3rec_catalogue_bce(F.detach().contiguous(), T.detach().contiguous(), zscale, yscale,
+                                                     key, tgt_ptr, tgt_idx, want_dF=bool(need and ctx.needs_input_grad[0]),
+                                                     want_dT=bool(need and ctx.needs_input_grad[1]), err_flag=flag)
+        ctx.grads = (dF, dT)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dF, dT = ctx.grads
+        return (None if dF is None else dF * g, None if dT is None else dT * g, None, None, None, None, None, None)

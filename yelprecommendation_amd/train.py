@@ -193,11 +193,12 @@ def train(cfg, args):
 
 
 def _train_s3rec(cfg, args):
-    """reference train.py:104-115: fine-tuning (the pre-training of :105-109 is not built)."""
-    if cfg.get("pretrain"):
-        raise NotImplementedError("S3Rec pre-training is not built (pretrain=true): only fine-tuning runs here; a "
-                                  "best_pretrain_model.pt in model_dir is loaded when load_pretrain is set")
-    from .trainers.s3rec_trainer import S3RecTrainer
+    """reference train.py:104-115: with pretrain=true the pre-training of :105-109 on the train loader first (its
+    best model is what S3RecTrainer then picks up through load_pretrain), then fine-tuning."""
+    if cfg.get("pretrain") and str(cfg.device).lower() != "cuda":
+        raise NotImplementedError(f"S3Rec pre-training is not built for the {cfg.device} device (pretrain=true): the "
+                                  "kernels run on the GPU only")
+    from .trainers.s3rec_trainer import S3RecPreTrainer, S3RecTrainer
     if cfg.get("fast_loader"):
         # device-side batch builder instead of DataLoader(S3RecDataset): same law, own RNG
         import torch
@@ -209,6 +210,11 @@ def _train_s3rec(cfg, args):
         train_dataloader = DataLoader(args.train_dataset, batch_size=cfg.batch_size, shuffle=cfg.shuffle)
         valid_dataloader = DataLoader(args.valid_dataset, batch_size=cfg.batch_size, shuffle=cfg.shuffle)
         test_dataloader = DataLoader(args.test_dataset, batch_size=cfg.batch_size)
+    if cfg.get("pretrain"):
+        pretrainer = S3RecPreTrainer(cfg, args.model_info['num_items'], args.data_pipeline.item2attributes,
+                                     args.data_pipeline.attributes_count)
+        pretrainer.pretrain(train_dataloader)
+        pretrainer.load_best_model()
     trainer = S3RecTrainer(cfg, args.model_info['num_items'], args.data_pipeline.item2attributes,
                            args.data_pipeline.attributes_count)
     trainer.run(train_dataloader, valid_dataloader)

@@ -1,5 +1,5 @@
-"""S3Rec trainer — drop-in for ``S3RecTrainer`` of reference trainers/s3rec_trainer.py:173-314 (fine-tuning; the
-pre-training trainer of :18-171 is not built).
+"""S3Rec trainers — drop-ins for ``S3RecTrainer`` of reference trainers/s3rec_trainer.py:173-314 (fine-tuning, below)
+and for ``S3RecPreTrainer`` of :21-171 (pre-training: see the class).
 
 Same constructor ``S3RecTrainer(cfg, num_items, item2attributes, attributes_count)``; batches are dicts with the
 reference's keys (``X``, ``pos_items``, ``neg_items``; ``pos_item`` for the test loader).
@@ -26,6 +26,154 @@ from ..metric import ranking_metrics
 from ..models.s3rec import S3Rec
 from ..utils import logger
 from .base_trainer import BaseTrainer
+
+
+def attribute_csr(item2attributes, num_items, attributes_count):
+    """(ptr [num_items + 2], idx) int64 on the host: the categories of item id k (``item2attributes[k]['categories']``,
+    the reference's dict: key 0 is the pad and has none, a missing key has none), ascending and duplicate-free inside
+    an item.  An attribute id outside [0, attributes_count) raises ValueError."""
+    lists = []
+    for k in range(num_items + 1):
+        entry = item2attributes.get(k) if item2attributes is not None else None
+        cats = sorted(set(int(a) for a in (entry['categories'] if entry is not None else ())))
+        if k == 0:
+            cats = []                                      # aap_actual of the pad is all zero (decision 2)
+        if cats and not 0 <= cats[0] <= cats[-1] < attributes_count:
+            raise ValueError(f"S3RecPreTrainer: item {k} has an attribute id outside [0, {attributes_count}): {cats}")
+        lists.append(cats)
+    ptr = np.zeros(num_items + 2, dtype=np.int64)
+    np.cumsum([len(c) for c in lists], out=ptr[1:])
+    return ptr, np.fromiter((a for c in lists for a in c), dtype=np.int64, count=int(ptr[-1]))
+
+
+class S3RecPreTrainer(BaseTrainer):
+    """Drop-in for ``S3RecPreTrainer`` of reference trainers/s3rec_trainer.py:21-171.
+
+    ``train(loader)`` is :118-167 per batch — ``item_level_masking``, ``segment_masking``, the four losses, their sum,
+    ``backward``, ``step`` — and returns the SUM of the batch losses.  It reads only ``data['X']``: the reference's
+    dense ``aap_actual`` / ``mip_actual`` ([B, L, num_items + 1] float64 built in Python loops) are replaced by X itself
+    and an item -> categories CSR built once on the device, and the losses go through ``S3Rec.pretrain_loss`` (the
+    catalogue-BCE kernel).  Works on the batches of ``DataLoader(S3RecDataset)`` and of ``S3RecBatchLoader``.
+
+    ``segment_masking`` (:96-115): per row a segment length uniform in [2, L // 2 - 1] (``max_seq_len >= 6``) and a start
+    uniform in [0, L - len - 1]; the segment is right-aligned into the positive sequence.  The reference's loop
+    ``while neg_user_idx != i`` can only end at ``i``, so its negative segment comes from the SAME row at another,
+    independently drawn start: that is the default, ``sp_negative="same_row"``.  ``sp_negative="other_row"`` draws a
+    different row of the batch (B >= 2), the documented intent.  Both masking functions run vectorised on the device
+    from a generator the trainer owns, seeded from ``cfg.seed``; nothing replays the reference's host RNG stream.
+
+    ``pretrain(loader)`` is :59-89: ``best_pretrain_model.pt`` on every improvement of the TRAINING loss when
+    ``best_metric == 'loss'``, early stopping on ``patience``.  On a non-cuda device ``train`` / ``pretrain`` raise
+    NotImplementedError."""
+
+    def __init__(self, cfg, num_items: int, item2attributes, attributes_count: int, sp_negative: str = "same_row") -> None:
+        super().__init__(cfg)
+        if sp_negative not in ("same_row", "other_row"):
+            raise ValueError(f"S3RecPreTrainer: sp_negative {sp_negative!r} (same_row or other_row)")
+        self.num_items, self.attributes_count = num_items, attributes_count
+        self.item2attribute = item2attributes
+        self.sp_negative = sp_negative
+        ptr, idx = attribute_csr(item2attributes, num_items, attributes_count)       # validated on the host
+        self.model = S3Rec(self.cfg, num_items, attributes_count).to(self.device)
+        self.optimizer = self._optimizer(self.cfg.optimizer, self.model, self.cfg.lr)
+        self.attr_ptr, self.attr_idx = torch.from_numpy(ptr).to(self.device), torch.from_numpy(idx).to(self.device)
+        self._gen = None
+
+    def _generator(self):
+        if self._gen is None:
+            self._gen = torch.Generator(device=self.device).manual_seed(int(self.cfg.get("seed", 0)))
+        return self._gen
+
+    def _is_surpass_best_metric(self, **metric) -> bool:
+        return self.cfg.best_metric == 'loss' and metric['current'][0] < metric['best'][0]
+
+    def _trainable(self, what):
+        if self.device.type != "cuda":
+            raise NotImplementedError(f"S3RecPreTrainer.{what}: pre-training is not built for the {self.device.type} "
+                                      "device (the kernels run on the GPU only)")
+
+    def item_level_masking(self, sequences):
+        # reference s3rec_trainer.py:91-94: keeps the items where the mask is set
+        masks = torch.rand(sequences.shape, device=sequences.device, generator=self._generator()) < self.cfg.mask_portion
+        return masks, masks * sequences
+
+    def segment_masking(self, sequences):
+        # reference s3rec_trainer.py:96-115, every row at once
+        B, L = sequences.shape
+        if L < 6:
+            raise ValueError(f"S3RecPreTrainer.segment_masking: max_seq_len {L} leaves no segment length in "
+                             "[2, L // 2 - 1] (6 is the least)")
+        dev, gen = sequences.device, self._generator()
+
+        def randint(high):                                  # uniform in [0, high[b]) per row
+            u = torch.rand(B, device=dev, generator=gen, dtype=torch.float64)
+            return torch.minimum((u * high).long(), high - 1)
+
+        seg_len = 2 + randint(torch.full((B,), L // 2 - 2, device=dev))
+        start = randint(L - seg_len)
+        neg_start = randint(L - seg_len)
+        rows = torch.arange(B, device=dev)
+        if self.sp_negative == "other_row":
+            if B < 2:
+                raise ValueError("S3RecPreTrainer: sp_negative='other_row' needs a batch of at least two rows")
+            neg_rows = (rows + 1 + randint(torch.full((B,), B - 1, device=dev))) % B
+        else:
+            neg_rows = rows
+        at = torch.arange(L, device=dev)[None, :]
+        inside = (at >= start[:, None]) & (at < (start + seg_len)[:, None])
+        tail = at >= (L - seg_len)[:, None]                 # the right-aligned places
+        src = (at - (L - seg_len)[:, None]).clamp(min=0)    # offset inside the segment
+        pos = torch.where(tail, torch.gather(sequences, 1, (start[:, None] + src).clamp(max=L - 1)), 0)
+        neg = torch.where(tail, torch.gather(sequences[neg_rows], 1, (neg_start[:, None] + src).clamp(max=L - 1)), 0)
+        return torch.where(inside, 0, sequences), pos, neg
+
+    def train(self, train_dataloader) -> float:
+        self._trainable("train")
+        self.model.train()
+        self._loss_accum.zero_()
+        for data in train_dataloader:
+            sequences = data['X'].to(self.device)
+            masks, item_masked = self.item_level_masking(sequences)
+            _segment_masked, pos_segments, neg_segments = self.segment_masking(sequences)
+            losses = self.model.pretrain_loss(sequences, masks, item_masked, pos_segments, neg_segments, self.attr_ptr,
+                                              self.attr_idx)
+            self.optimizer.zero_grad()
+            loss = losses[0] + losses[1] + losses[2] + losses[3]
+            loss.backward()
+            self.optimizer.step()
+            self._accumulate(loss)
+        self.model.check_indices()
+        return float(self._loss_accum.item())
+
+    def pretrain(self, train_dataset):
+        self._trainable("pretrain")
+        logger.info("[Pre-Trainer] run...")
+        best_train_loss = 1e+6
+        endurance = 0
+        for epoch in range(self.cfg.pretrain_epochs):
+            train_loss = self.train(train_dataset)
+            logger.info(f"[Pre-Trainer] epoch: {epoch} > pretrain loss: {train_loss:.4f}")
+            if self._is_surpass_best_metric(current=(train_loss,), best=(best_train_loss,)):
+                logger.info("[Trainer] update best model...")
+                best_train_loss = train_loss
+                endurance = 0
+                torch.save(self.model.state_dict(), f'{self.cfg.model_dir}/best_pretrain_model.pt')
+            else:
+                endurance += 1
+                if endurance > self.cfg.patience:
+                    logger.info("[Trainer] ealry stopping...")
+                    break
+
+    def load_best_model(self):
+        logger.info("[Trainer] Load best model...")
+        self.model.load_state_dict(torch.load(f'{self.cfg.model_dir}/best_pretrain_model.pt', map_location=self.device,
+                                              weights_only=True))
+
+    def validate(self, valid_dataloader):
+        raise NotImplementedError("S3RecPreTrainer has no validation: the reference's pre-training watches its training loss")
+
+    def evaluate(self, test_dataloader):
+        raise NotImplementedError("S3RecPreTrainer has no evaluation: fine-tune with S3RecTrainer")
 
 
 class S3RecTrainer(BaseTrainer):
