@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YR_ENGINE_VERSION 35
+#define YR_ENGINE_VERSION 36
 
 #define YR_ERR_UNSUPPORTED (-1) /* embedding width / option not compiled in   */
 #define YR_ERR_BADARG      (-2) /* null pointer, negative size, misalignment  */
@@ -912,6 +912,41 @@ int yr_s3rec_catalogue_bce(const float *F, const float *T, const float *zscale, 
                            const int64_t *key, const int64_t *tgt_ptr, const int64_t *tgt_idx, int64_t N, int64_t R,
                            int64_t K, int E, float *loss, float *row_loss, float *dF, float *dT, float *workspace,
                            int64_t workspace_floats, int32_t *err_flag, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * S3Rec full-catalogue evaluation: the rank of the held-out item   (reference trainers/s3rec_trainer.py:264-283:
+ *   the place of pos_item among itself and 99 sampled negatives — here over the whole catalogue;
+ *   csrc/s3rec_rank.hip)
+ * H [N][E] (the encoder's last rows) against every row of T [R][E] (item_embedding.weight, R = num_items + 1), both
+ * f32 and 16-byte aligned:  s[n, r] = <H[n], T[r]>  in f32 on v_mfma_f32_32x32x2_f32.  Columns below first_col (0 or
+ * 1; S3Rec passes 1, the pad row) are never candidates.
+ *   rank[n] = the number of columns r in [first_col, R), r != target[n], r not excluded for row n, with
+ *             s[n, r] > s[n, target[n]], or s[n, r] == s[n, target[n]] and r < target[n]
+ * — the project's list order (score descending, item id ascending among equal scores), so rank is the 0-based place
+ * the target would take in an unbounded yr_mf_eval_topk list.  target_score[n] = s[n, target[n]] (may be null).
+ * The exclude list of row n is row excl_rows[n] (excl_rows null: row n) of the CSR excl_ptr [K + 1] / excl_idx,
+ * ascending and duplicate-free inside a row; excl_ptr = excl_idx = null: nothing is excluded.  An entry equal to the
+ * row's target is ignored (the target is never excluded); an entry outside [0, R) is no column; a row index outside
+ * [0, K) raises YR_FLAG_BAD_USER and excludes nothing.
+ * target[n] in [0, first_col) means "no target": rank[n] = -1, target_score[n] = 0, no flag; target[n] < 0 or >= R
+ * gives the same values and raises YR_FLAG_BAD_ITEM (nothing is dereferenced).
+ * One arithmetic: the target's score and every column's score come from the same instruction sequence in the same k
+ * order (the target's from a first tile whose swept rows are the owned rows' targets), so a row of T bit-identical
+ * to the target's row ties exactly and the id decides.  Counts are integers, added over lanes, waves and chunks of
+ * 2,048 columns (per-chunk partial counts in the workspace, then one small kernel): no float atomics, no [N][R]
+ * array; a row's rank does not depend on N, on its place in the batch or on the other rows, and two calls give one
+ * answer bit for bit.
+ * workspace: yr_s3rec_catalogue_rank_workspace_bytes(N, R, E) bytes (a negative YR_ERR_* for refused sizes), 4-byte
+ * aligned, any contents.  Checked before any launch: negative sizes, E <= 0, first_col outside {0, 1}:
+ * YR_ERR_BADARG; a width outside 16 / 32 / 64 / 128: YR_ERR_UNSUPPORTED; then N == 0 or R == 0: 0 (nothing is
+ * written); then null or misaligned pointers, one half of the CSR without the other, a workspace too small:
+ * YR_ERR_BADARG.
+ * ------------------------------------------------------------------------- */
+int64_t yr_s3rec_catalogue_rank_workspace_bytes(int64_t N, int64_t R, int E);
+int yr_s3rec_catalogue_rank(const float *H, const float *T, const int64_t *target, const int64_t *excl_ptr,
+                            const int64_t *excl_idx, const int64_t *excl_rows, int64_t N, int64_t R, int64_t K, int E,
+                            int64_t first_col, int64_t *rank, float *target_score, void *workspace,
+                            int64_t workspace_bytes, int32_t *err_flag, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Device-side S3Rec sequence batches  (reference data/datasets/s3rec_data_pipeline.py:13-50: split +

@@ -73,6 +73,11 @@ BUDGETS = [
     (r"void yr::s3rec_cbce_kernel<128, (true|false)>", 512, 17 * 1024,
      "as above at E = 128: 64 + 64 row registers, one wave per SIMD; 16.1 KB of LDS for the wave-order sum; no scratch"),
     (r"yr::s3rec_cbce_(reduce|loss)_kernel", 64, 3 * 1024, "streaming sums in a fixed order"),
+    (r"void yr::s3rec_rank_kernel<(16|32|64)>", 128, 1024,
+     "S3Rec full-catalogue rank: the owned rows (E / 2 registers) beside one tile of scores and nothing else, so "
+     "four waves per SIMD (512 / 4 -> 128): more than the two workgroups per CU of the cbce kernel; no scratch"),
+    (r"void yr::s3rec_rank_kernel<128>", 256, 1024, "as above at E = 128: 64 row registers, two waves per SIMD"),
+    (r"yr::s3rec_rank_sum_kernel", 64, 0, "streaming integer sums of the chunks' counts"),
 ]
 # Scratch (spilled registers) per lane.  The forms the benchmark and the trainers run by default — width 64, summation
 # order free — must have none; the deterministic-order forms and some forms of the other widths are held at 64 VGPRs by

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # YR_ENGINE_LIB: measurement hook — an instrumented build of the same sources (scratch/inst_build.sh writes it to
 # a temp directory so that the product objects and library are never overwritten); unset in every product run.
 LIB_PATH = os.environ.get("YR_ENGINE_LIB") or os.path.join(_HERE, "libyelprec_engine.so")
-ENGINE_VERSION = 35
+ENGINE_VERSION = 36
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -129,6 +129,8 @@ SIGNATURES = {
     "yr_s3rec_item_grad": [_p, _p, _p, _p, _p, _p, _i64, _int, _i64, _p, _p, _p, _p],
     "yr_s3rec_catalogue_bce_workspace_floats": [_i64, _i64, _int],
     "yr_s3rec_catalogue_bce": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _p, _p, _p, _p, _p, _i64, _p, _p],
+    "yr_s3rec_catalogue_rank_workspace_bytes": [_i64, _i64, _int],
+    "yr_s3rec_catalogue_rank": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _i64, _p, _p, _p, _i64, _p, _p],
     "yr_s3rec_batches": [_p, _p, _p, _p, _i64, _i64, _p, _i64, _int, _int, _int, C.c_uint64, C.c_uint64, _p, _p, _p, _p,
                          _p],
 }
@@ -140,7 +142,7 @@ RESTYPES.update({name: _i64 for name in (
     "yr_bpr_mf_pull_workspace_bytes", "yr_rank_metrics_workspace_bytes", "yr_cdae_sparse_part_columns",
     "yr_cdae_decode_loss_partials", "yr_mf_eval_topk_workspace_bytes", "yr_mf_eval_topk_planes_bytes",
     "yr_ngcf_step_workspace_bytes", "yr_s3rec_train_workspace_floats",
-    "yr_s3rec_catalogue_bce_workspace_floats")})
+    "yr_s3rec_catalogue_bce_workspace_floats", "yr_s3rec_catalogue_rank_workspace_bytes")})
 
 _lib = None
 

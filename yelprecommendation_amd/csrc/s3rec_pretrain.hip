@@ -26,7 +26,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "s3rec_cb.h"     // the tile geometry, cb_acc_row, cb_lower_bound, cb_mask: shared with csrc/s3rec_rank.hip
 
 namespace yr {
 
@@ -35,6 +35,9 @@ constexpr int kCbTilesPerWave = 16;         // column tiles a wave sweeps in the
 constexpr int kCbColChunk = kWavesPerBlock * kCbTilesPerWave * kCbTile;   // 2,048 columns per workgroup
 constexpr int kCbGridMax = 2048;            // workgroups per launch; the kernels' own loops go on from there
 constexpr int kCbLossBlock = 256;           // threads of the single workgroup that adds row_loss up
+
+static_assert(kCbTile == kSweepTile && kCbTilesPerWave == kSweepTilesPerWave && kCbColChunk == kSweepColChunk &&
+                  kCbGridMax == kSweepGridMax, "one geometry for the catalogue sweeps (s3rec_cb.h)");
 
 struct Cbce {
   const float* F;             // [N][E]
@@ -50,31 +53,6 @@ struct Cbce {
   int64_t chunks;
   int32_t* err_flag;
 };
-
-__device__ __forceinline__ int cb_acc_row(int q, int lane) { return (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5); }
-
-// first k in [lo, hi) with idx[k] >= v
-__device__ __forceinline__ int64_t cb_lower_bound(const int64_t* __restrict__ idx, int64_t lo, int64_t hi, int64_t v) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (idx[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// bit c of the result: column c0 + c is a target.  `cur` walks the key's ascending list and stays at the first entry
-// not below c0 + 32
-__device__ __forceinline__ uint32_t cb_mask(const int64_t* __restrict__ idx, int64_t& cur, int64_t end, int64_t c0) {
-  uint32_t m = 0;
-  while (cur < end) {
-    const int64_t v = idx[cur];
-    if (v >= c0 + kCbTile) break;
-    if (v >= c0) m |= 1u << (int)(v - c0);
-    ++cur;
-  }
-  return m;
-}
 
 template <int E, bool ROWS>
 __global__ __launch_bounds__(kBlock, E <= 64 ? 2 : 1) void s3rec_cbce_kernel(Cbce p) {

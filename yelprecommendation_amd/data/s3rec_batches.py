@@ -53,6 +53,29 @@ class S3RecSequences:
         self.avoid_ptr = torch.zeros(self.num_users + 1, dtype=torch.int64, device=self.device)
         self.avoid_ptr[1:] = torch.cumsum(torch.bincount(owner, minlength=self.num_users), 0)
         self.flag = engine.new_error_flag(self.device)
+        self._history = {}
+
+    def history(self, mode):
+        """(ptr [num_users + 1], idx) on the device: row u holds the ascending, duplicate-free ``id + 1`` of
+        ``row[0, max(0, n - cut))`` with cut = 3 / 2 / 1 for 'train' / 'valid' / 'test' — every interaction the model
+        may see for that mode (not only the last ``max_seq_len``), the exclude lists of full-catalogue evaluation.
+        Always the items themselves, whatever ``shifted``; built once per mode."""
+        if mode not in MODES:
+            raise ValueError(f"mode {mode!r}")
+        if mode not in self._history:
+            cut = 3 - MODES.index(mode)
+            n = self.beh_ptr[1:] - self.beh_ptr[:-1]
+            user = torch.repeat_interleave(torch.arange(self.num_users, device=self.device), n)
+            at = torch.arange(self.beh_idx.numel(), device=self.device) - self.beh_ptr[:-1][user]
+            value = self.beh_idx + 1
+            keep = (at < (n - cut)[user]) & (value >= 1) & (value <= self.num_items)
+            span = self.num_items + 1
+            keys = torch.unique(user[keep] * span + value[keep])
+            owner = torch.div(keys, span, rounding_mode="floor")
+            ptr = torch.zeros(self.num_users + 1, dtype=torch.int64, device=self.device)
+            ptr[1:] = torch.cumsum(torch.bincount(owner, minlength=self.num_users), 0)
+            self._history[mode] = (ptr, (keys - owner * span).contiguous())
+        return self._history[mode]
 
     @classmethod
     def from_frame(cls, df, num_items, max_seq_len, device, seed=0, shifted=False):

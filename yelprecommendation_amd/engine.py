@@ -1592,6 +1592,47 @@ def s3rec_catalogue_bce(F, T, zscale, yscale, key, tgt_ptr=None, tgt_idx=None, g
     return loss, row_loss, dF, dT
 
 
+# ---- S3Rec full-catalogue evaluation (csrc/s3rec_rank.hip: the catalogue rank) ----
+def s3rec_catalogue_rank_workspace_bytes(N, R, E):
+    """Bytes of the catalogue-rank workspace (yr_s3rec_catalogue_rank_workspace_bytes)."""
+    n = _lib.load().yr_s3rec_catalogue_rank_workspace_bytes(N, R, E)
+    if n < 0:
+        check(int(n), "yr_s3rec_catalogue_rank_workspace_bytes")
+    return int(n)
+
+
+def s3rec_catalogue_rank(H, T, target, excl_ptr=None, excl_idx=None, excl_rows=None, first_col=1, want_score=False,
+                         err_flag=None):
+    """rank [N] int64 of yr_s3rec_catalogue_rank: the 0-based place of column ``target[n]`` among the columns
+    [first_col, R) of <H[n], T[r]> in the list order (score descending, id ascending among equal scores), the columns
+    of CSR row ``excl_rows[n]`` (default n) of ``excl_ptr`` / ``excl_idx`` (ascending inside a row) left out; -1 for a
+    row without a target.  ``want_score`` True: (rank, target_score [N] float32)."""
+    lib = _lib.load()
+    f32, i64 = torch.float32, torch.int64
+    if H.dim() != 2 or T.dim() != 2 or H.shape[1] != T.shape[1]:
+        raise EngineError(f"s3rec_catalogue_rank: H [N, E] and T [R, E] expected, got {tuple(H.shape)} / {tuple(T.shape)}")
+    (N, E), R = H.shape, T.shape[0]
+    if target.numel() != N or (excl_rows is not None and excl_rows.numel() != N):
+        raise EngineError("s3rec_catalogue_rank: target (and excl_rows) hold one entry per row of H")
+    if (excl_ptr is None) != (excl_idx is None):
+        raise EngineError("s3rec_catalogue_rank: excl_ptr and excl_idx come together")
+    K = 0 if excl_ptr is None else excl_ptr.numel() - 1
+    dev = H.device
+    ws_bytes = s3rec_catalogue_rank_workspace_bytes(N, R, E)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    rank = torch.empty(N, dtype=i64, device=dev)
+    score = torch.empty(N, dtype=f32, device=dev) if want_score else None
+    # an empty CSR has no storage to point at: its offsets array stands in (never dereferenced: every list is empty)
+    idx = None if excl_idx is None else (_dev(excl_idx, i64, "excl_idx") if excl_idx.numel() else _dev(excl_ptr, i64, "excl_ptr"))
+    check(lib.yr_s3rec_catalogue_rank(_dev(H, f32, "H"), _dev(T, f32, "T"), _dev(target, i64, "target"),
+                                      _opt(excl_ptr, i64, "excl_ptr"), idx, _opt(excl_rows, i64, "excl_rows"), N, R, K,
+                                      E, int(first_col), rank.data_ptr() if N else None,
+                                      score.data_ptr() if want_score and N else None,
+                                      ws.data_ptr() if ws.numel() else None, ws_bytes,
+                                      _opt(err_flag, torch.int32, "flag"), _stream()), "yr_s3rec_catalogue_rank")
+    return (rank, score) if want_score else rank
+
+
 S3REC_MODES = {"train": 0, "valid": 1, "test": 2}          # YR_S3REC_TRAIN / VALID / TEST
 S3REC_MAX_NEG = 128
 

@@ -31,6 +31,12 @@ reference computes and never consumes, is skipped.  ``pretrain_loss`` gives the 
 trainers/s3rec_trainer.py:137-158 through the catalogue-BCE kernel (csrc/s3rec_pretrain.hip): no [B, L, num_items +
 1] array exists in its forward or backward.  On CPU tensors all three raise NotImplementedError.
 
+Full-catalogue evaluation (new; the reference ranks the held-out item against 99 sampled negatives only).
+``rank_catalogue(X, target, history, users)`` gives the exact 0-based place of one item per sequence among ALL items
+(csrc/s3rec_rank.hip: no [B, num_items + 1] array), ``recommend(X, k, history, users)`` the top-k item ids through the
+fused list sweep the other models evaluate with; both run the ``last_only`` encoder, in eval() mode under
+``torch.no_grad()`` on CUDA tensors only.
+
 Supported: embed_size 16 / 32 / 64 / 128, max_seq_len 1 .. 64, 1 .. 4 heads, 1 .. 4 blocks; anything else raises
 NotImplementedError at construction.
 """
@@ -230,6 +236,78 @@ class S3Rec(BaseModel):
         h_last = self._encode(X, last_only=True)
         return engine.s3rec_candidate_scores(self.item_embedding.weight.detach(), h_last, pos_item.contiguous(),
                                              neg_items.contiguous(), err_flag=self._flag())
+
+    # -- full-catalogue evaluation (csrc/s3rec_rank.hip; the lists through engine.mf_recommend) ----------------
+    def _catalogue_rows(self, what, X, history, users):
+        """The checks of the two full-catalogue entry points and the CSR rows of the batch: (ptr, idx, rows) or
+        (None, None, None) without a history."""
+        self._scoring_only(what)
+        if not self.item_embedding.weight.is_cuda or not X.is_cuda:
+            raise NotImplementedError(f"S3Rec.{what}: full-catalogue evaluation is not built for CPU tensors (the "
+                                      "kernels run on the GPU only): move the model and the batch to the device")
+        if history is None:
+            return None, None, None
+        ptr, idx = history
+        rows = torch.arange(X.shape[0], device=X.device) if users is None else users.to(X.device).long().contiguous()
+        if rows.numel() != X.shape[0]:
+            raise ValueError(f"S3Rec.{what}: users must hold one CSR row per sequence")
+        return ptr, idx, rows
+
+    def _catalogue_lists(self, h_last, k, ptr, idx, rows, target=None):
+        """[B, k] int64 item ids 1..num_items, best first, -1 where a row has fewer than k free items: the rows' history
+        lists gathered into a batch CSR in the 0-based space of ``item_embedding.weight[1:]`` (index preparation), then
+        engine.mf_recommend.  ``target`` [B]: an entry equal to the row's target is dropped, as the rank sweep does."""
+        B, dev = h_last.shape[0], h_last.device
+        mptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        midx = torch.zeros(0, dtype=torch.int64, device=dev)
+        K = 0 if ptr is None else ptr.numel() - 1
+        if K > 0 and B > 0:
+            ok = (rows >= 0) & (rows < K)
+            self._flag().bitwise_or_((~ok).any().to(torch.int32) * engine.FLAG_BAD_USER)
+            r = rows.clamp(0, K - 1)
+            start = ptr[r]
+            n = torch.where(ok, ptr[r + 1] - start, torch.zeros_like(start))
+            row_of = torch.repeat_interleave(torch.arange(B, device=dev), n)
+            first = torch.cumsum(n, 0) - n
+            vals = idx[start[row_of] + torch.arange(row_of.numel(), device=dev) - first[row_of]]
+            keep = (vals >= 1) & (vals <= self.num_items)
+            if target is not None:
+                keep &= vals != target[row_of]
+            row_of, midx = row_of[keep], (vals[keep] - 1).contiguous()
+            mptr[1:] = torch.cumsum(torch.bincount(row_of, minlength=B), 0)
+        table = self.item_embedding.weight.detach()[1:]
+        lists = engine.mf_recommend(h_last, table, torch.arange(B, device=dev), mptr, midx, int(k))
+        free = self.num_items - (mptr[1:] - mptr[:-1])
+        return torch.where(torch.arange(int(k), device=dev)[None, :] < free[:, None], lists + 1,
+                           torch.full_like(lists, -1))
+
+    def rank_catalogue(self, X, target, history=None, users=None):
+        """int64 [B]: the 0-based place of item ``target[b]`` (1..num_items; 0: no target, -1) among ALL items by the
+        score <h[b, L - 1], item_embedding.weight[r]>, score descending and id ascending among equal scores, the pad
+        row never a candidate.  ``history`` = (ptr, idx), a CSR of ascending 1-based item ids per user
+        (``S3RecSequences.history``): row ``users[b]`` (default b) is left out of the count, except the target itself.
+        eval() mode under torch.no_grad(), CUDA tensors; ids go through the model's error flag."""
+        ptr, idx, rows = self._catalogue_rows("rank_catalogue", X, history, users)
+        h_last = self._encode(X, last_only=True)
+        return engine.s3rec_catalogue_rank(h_last, self.item_embedding.weight.detach(), target.contiguous(), ptr, idx,
+                                           rows, first_col=1, err_flag=self._flag())
+
+    def recommend(self, X, k, history=None, users=None):
+        """int64 [B, k]: the k best item ids (1..num_items) for each sequence, best first, the row's history left out
+        and the pad never returned; rows with fewer than k free items are padded with -1.  Same modes as
+        ``rank_catalogue``."""
+        ptr, idx, rows = self._catalogue_rows("recommend", X, history, users)
+        return self._catalogue_lists(self._encode(X, last_only=True), k, ptr, idx, rows)
+
+    def rank_and_recommend(self, X, target, k, history=None, users=None):
+        """(rank_catalogue, recommend) from one run of the encoder, the lists keeping the target as the rank does: a
+        row's target is in its list exactly when its rank is below k (up to float near-ties between the sweeps)."""
+        ptr, idx, rows = self._catalogue_rows("rank_and_recommend", X, history, users)
+        h_last = self._encode(X, last_only=True)
+        target = target.contiguous()
+        rank = engine.s3rec_catalogue_rank(h_last, self.item_embedding.weight.detach(), target, ptr, idx, rows,
+                                           first_col=1, err_flag=self._flag())
+        return rank, self._catalogue_lists(h_last, k, ptr, idx, rows, target=target)
 
     # -- pre-training (reference models/s3rec.py:117-181) ----------------------------------------------------
     def _pretrain_on_device(self, what):

@@ -6,6 +6,7 @@ the reference's layout (or the built-in defaults) plus ``key=value`` overrides.
     python -m yelprecommendation_amd.train model_name=MF synthetic=yelp2018 fast_loader=true
     python -m yelprecommendation_amd.train model_name=DCN synthetic=yelp2018 fast_loader=true hidden_dims=[64,32]
     python -m yelprecommendation_amd.train model_name=S3Rec synthetic=yelp2018 fast_loader=true batch_size=256
+    python -m yelprecommendation_amd.train model_name=S3Rec synthetic=yelp2018 fast_loader=true full_eval=true
 
 Call order is the reference's: pipeline.preprocess() -> split() -> datasets -> set_seed() ->
 DataLoaders -> trainer.run() -> load_best_model() -> evaluate(test).
@@ -219,7 +220,15 @@ def _train_s3rec(cfg, args):
                            args.data_pipeline.attributes_count)
     trainer.run(train_dataloader, valid_dataloader)
     trainer.load_best_model()
-    return trainer, trainer.evaluate(test_dataloader)
+    result = trainer.evaluate(test_dataloader)
+    if cfg.get("full_eval"):
+        # the held-out item against the whole catalogue, the user's earlier items left out (logged; the return value
+        # stays the reference's sampled protocol)
+        import torch
+        if not cfg.get("fast_loader"):
+            store = args.test_dataset.to_sequences(torch.device(cfg.device), cfg.max_seq_len, seed=cfg.seed)
+        trainer.evaluate_full(test_dataloader, history=store.history('test'))
+    return trainer, result
 
 
 def run(cfg, args):

@@ -15,12 +15,16 @@ reference's keys (``X``, ``pos_items``, ``neg_items``; ``pos_item`` for the test
   computes them (s3rec_trainer.py:265-314): ``predicted`` is its odd array — the positive's id where the positive
   lands in the top-n, 0 elsewhere — fed to the same metric functions.  The positive's rank is the number of negatives
   scoring strictly higher (the reference's ``argsort`` leaves ties to the sort; its recorded runs have none).
+* ``evaluate_full`` (new) ranks the held-out item against the WHOLE catalogue, the user's earlier items left out: the
+  four metrics by the protocol and the code of ``MFTrainer.evaluate`` (comparable across the five models), and
+  HR@k / NDCG@k / MRR from the exact ranks in ``last_full_eval``.  ``evaluate`` is unchanged.
 """
 import os
 
 import numpy as np
 import torch
 
+from .. import engine
 from ..loss import BPRLoss
 from ..metric import ranking_metrics
 from ..models.s3rec import S3Rec
@@ -275,6 +279,55 @@ class S3RecTrainer(BaseTrainer):
         actual = pos_ids.reshape(-1, 1).tolist()
         p, r, m, n = ranking_metrics(actual, predicted, k)
         self._log_test(p, r, m, n)
+        return (p, r, m, n)
+
+    @torch.no_grad()
+    def evaluate_full(self, dataloader, history=None) -> tuple:
+        """(precision, recall, MAP, NDCG)@top_n of the held-out item against the WHOLE catalogue — the protocol and
+        the code of ``MFTrainer.evaluate`` (fused lists, then ``engine.rank_metrics``: reference metric.py with its
+        quirks), so the figures stand next to the other models'.  The target is ``pos_item`` (test batches) or
+        ``pos_items[:, -1]`` (valid batches), the exclude rows are ``user_id``'s of ``history`` = (ptr, idx)
+        (``S3RecSequences.history(mode)``; None masks nothing but the pad).  Sets ``last_full_eval``: the exact ranks
+        ρ of all rows (device, -1 without a target), ``n_users`` (rows with a target), ``n_skipped``, and from the ranks
+        in float64, as means over the rows with a target, ``HR@k`` = [ρ < k], ``NDCG@k`` = [ρ < k] / log2(ρ + 2) for
+        k in {1, 5, 10, top_n} and ``MRR`` = 1 / (ρ + 1)."""
+        self.model.eval()
+        dev = self.device
+        k = int(self.cfg.top_n)
+        ranks, lists, targets = [], [], []
+        for data in dataloader:
+            X = data['X'].to(dev)
+            target = (data['pos_item'] if 'pos_item' in data else data['pos_items'][:, -1]).to(dev).reshape(-1).long()
+            users = torch.as_tensor(data['user_id']).to(dev).reshape(-1).long()
+            rank, topk = self.model.rank_and_recommend(X, target, k, history=history, users=users)
+            ranks.append(rank)
+            lists.append(topk)
+            targets.append(target)
+        if not ranks:
+            raise ValueError("S3RecTrainer.evaluate_full: the loader gave no batch")
+        ranks, lists, targets = torch.cat(ranks), torch.cat(lists), torch.cat(targets)
+        has = ranks >= 0
+        pos_ptr = torch.zeros(ranks.numel() + 1, dtype=torch.int64, device=dev)
+        pos_ptr[1:] = torch.cumsum(has, 0)
+        four = engine.rank_metrics(lists.contiguous(), pos_ptr, targets[has].contiguous())[:4]
+        rho = ranks[has].to(torch.float64)
+        ks = sorted({1, 5, 10, k})
+        stats = [((rho < kk).to(torch.float64)).mean() for kk in ks]
+        stats += [((rho < kk).to(torch.float64) / torch.log2(rho + 2.0)).mean() for kk in ks]
+        stats += [(1.0 / (rho + 1.0)).mean(), has.sum().to(torch.float64)]
+        self.model.check_indices()
+        host = torch.cat([four, torch.stack(stats)]).tolist()       # the one read-back of the metrics
+        p, r, m, n = host[:4]
+        n_users = int(host[-1])
+        out = {"ranks": ranks, "n_users": n_users, "n_skipped": int(ranks.numel()) - n_users, "MRR": host[-2]}
+        for i, kk in enumerate(ks):
+            out[f"HR@{kk}"] = host[4 + i]
+            out[f"NDCG@{kk}"] = host[4 + len(ks) + i]
+        self.last_full_eval = out
+        self._log_test(p, r, m, n)
+        logger.info("[Trainer] full catalogue > " + " / ".join(
+            f"{name}: {out[name]:.4f}" for name in [f"HR@{kk}" for kk in ks] + [f"NDCG@{kk}" for kk in ks] + ["MRR"])
+            + f" / users: {n_users} (skipped {out['n_skipped']})")
         return (p, r, m, n)
 
     def _load_best_pretrain_model(self):
