@@ -588,6 +588,23 @@ int yr_mf_eval_topk_bias(const float *U, const float *I, const float *item_bias,
                          const int64_t *mask_ptr, const int64_t *mask_idx, float mask_value,
                          int k, int64_t *out, void *workspace, int64_t workspace_bytes, int mode,
                          const int64_t *hint, int32_t *err_flag, void *stream);
+/* yr_ngcf_eval_topk: the same for NGCF's score, the sum over the layer buffers of per-layer dot products
+ *   (reference models/ngcf.py:44-58 for ALL items of the catalogue):
+ *     s(r, j) = sum_l E_l[users[r]] . E_l[num_users + j],   l = 0 .. n_layers - 1,
+ *   every E_l [num_users + num_items, D] f32, users first; `layers` is a HOST array of n_layers
+ *   (1 .. YR_NGCF_MAX_LAYERS) device pointers.  D = 16, 32, 64, 128 and k <= 16 (YR_ERR_UNSUPPORTED otherwise).
+ *   One f32 accumulator per score over all n_layers * D products (v_mfma_f32_32x32x2_f32; layers ascending): the
+ *   layers are never concatenated and no score matrix is written.  No prescan and no split form.  Masks, order,
+ *   hint, err_flag and the -1 padding as yr_mf_eval_topk.
+ * workspace: yr_ngcf_eval_topk_workspace_bytes(nrows, num_items, n_layers, D, k) bytes, used in this order: 4 bytes
+ *   per row for the thresholds of hint lists, the per-slice partial lists.  Both are optional, as above: without
+ *   room the hint is ignored / the sweep runs as one slice. */
+int64_t yr_ngcf_eval_topk_workspace_bytes(int64_t nrows, int64_t num_items, int n_layers, int D, int k);
+int yr_ngcf_eval_topk(const float *const *layers, int n_layers, int D, const int64_t *users, int64_t nrows,
+                      int64_t num_users, int64_t num_items,
+                      const int64_t *mask_ptr, const int64_t *mask_idx, float mask_value,
+                      int k, int64_t *out, void *workspace, int64_t workspace_bytes,
+                      const int64_t *hint, int32_t *err_flag, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Masked row-wise top-k      (reference trainers/mf_trainer.py:163-178,

@@ -46,6 +46,13 @@ BUDGETS = [
      "slab sweep: two workgroups of four waves per CU = two waves per SIMD (512 / 2 -> 256), 2 x 72 KB of 160 KB LDS"),
     (r"void yr::mf_scores_mfma_wide_kernel<(256|512|1024)>", 256, 72 * 1024, "score GEMM in slabs: as the sweep"),
     (r"void yr::et_hint_bound_kernel<(256|512|1024)>", 64, 0, "the dot product is a loop: eight waves per SIMD"),
+    # NGCF's evaluation sweep over the layer tables
+    (r"void yr::ngcf_eval_topk_kernel<(16|32|64), (4|10|16)>", 168, 40 * 1024,
+     "layered sweep: a layer's half row (D / 2 registers) beside two accumulators and the list, at least three "
+     "workgroups per CU (512 / 3 -> 168; 36 KB of LDS each: two 32-item tiles of one to four layers + the candidate buffers)"),
+    (r"void yr::ngcf_eval_topk_kernel<128, (4|10|16)>", 256, 52 * 1024,
+     "as the wide sweep's slab of 128 dims: two workgroups per CU (512 / 2 -> 256), 2 x 49 KB of LDS"),
+    (r"void yr::ngcf_hint_bound_kernel<(16|32|64|128)>", 64, 0, "the dot product is a loop over the layers: eight waves per SIMD"),
     (r"void yr::adam_dual_wide_kernel<(true|false)>", 64, 1024, "streaming pass, as adam_dual_kernel"),
     # the wide hidden sizes (512 / 1024) of CDAE on list batches
     (r"void yr::cdae_sampled_decode_kernel<64, (8|16), true, (true|false)>", 128, 34 * 1024,

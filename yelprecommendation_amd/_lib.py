@@ -90,6 +90,8 @@ SIGNATURES = {
     "yr_mf_eval_topk_workspace_bytes": [_i64, _i64, _int, _int, _int],
     "yr_mf_eval_topk": [_p, _p, _p, _i64, _int, _i64, _i64, _p, _p, _f, _int, _p, _p, _i64, _int, _p, _p, _p],
     "yr_mf_eval_topk_bias": [_p, _p, _p, _p, _i64, _int, _i64, _i64, _p, _p, _f, _int, _p, _p, _i64, _int, _p, _p, _p],
+    "yr_ngcf_eval_topk_workspace_bytes": [_i64, _i64, _int, _int, _int],
+    "yr_ngcf_eval_topk": [_p, _int, _int, _p, _i64, _i64, _i64, _p, _p, _f, _int, _p, _p, _i64, _p, _p, _p],
     "yr_topk_masked": [_p, _i64, _i64, _i64, _p, _p, _p, _f, _int, _p, _p],
     "yr_rank_metrics_workspace_bytes": [_i64],
     "yr_rank_metrics": [_p, _i64, _int, _p, _p, _p, _p, _p, _p],
@@ -141,7 +143,7 @@ RESTYPES = {"yr_engine_arch": C.c_char_p}
 RESTYPES.update({name: _i64 for name in (
     "yr_bpr_mf_pull_workspace_bytes", "yr_rank_metrics_workspace_bytes", "yr_cdae_sparse_part_columns",
     "yr_cdae_decode_loss_partials", "yr_mf_eval_topk_workspace_bytes", "yr_mf_eval_topk_planes_bytes",
-    "yr_ngcf_step_workspace_bytes", "yr_s3rec_train_workspace_floats",
+    "yr_ngcf_step_workspace_bytes", "yr_ngcf_eval_topk_workspace_bytes", "yr_s3rec_train_workspace_floats",
     "yr_s3rec_catalogue_bce_workspace_floats", "yr_s3rec_catalogue_rank_workspace_bytes")})
 
 _lib = None

@@ -74,6 +74,9 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 __device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
+// NGCF's layer buffers E_0 .. E_K ([num_users + num_items, D] each), passed to a kernel by value
+struct LayerPtrs { const float* p[YR_NGCF_MAX_LAYERS]; };
+
 // Fast transcendental forms (v_exp_f32 / v_log_f32 / v_rcp_f32, about 1 ulp each) for the
 // per-triplet sigmoid / softplus: the library expf/log1pf/IEEE divide cost ~10x the instructions.
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }

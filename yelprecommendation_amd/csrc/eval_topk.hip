@@ -155,27 +155,25 @@ __global__ __launch_bounds__(kBlock) void et_split_rows_kernel(const float* __re
 // kernel's and the sweep's) can therefore differ by 2 (D + 2) 2^-24 A.  D = 64: 7.9e-6 A (3.9e-6 A each); 1.6e-5 is
 // that with a factor two to spare, kept as it is up to D = 128 (1.55e-5 A).  The wide widths take the same
 // expression with the first-order terms' slack: 2.18 (D + 2) 2^-24 = 1.3e-7 (D + 2) — 3.4e-5, 6.7e-5 and 1.33e-4
-// at D = 256, 512 and 1,024.  (Too small a margin would cost correctness; too large only candidates.)
+// at D = 256, 512 and 1,024.  (Too small a margin would cost correctness; too large only candidates.)  The
+// expression holds for any number of products: NGCF's layered score (ngcf_hint_bound_kernel) passes W = n_layers D,
+// 16 .. 1,024 — 2.5e-5 at the default W = 192.
 __host__ __device__ constexpr float et_hint_margin(int D) { return D <= 128 ? 1.6e-5f : 1.3e-7f * (float)(D + 2); }
 
-template <int D>
-__global__ __launch_bounds__(kBlock) void et_hint_bound_kernel(
-    const float* __restrict__ U, const float* __restrict__ I, const float* __restrict__ item_bias,
-    const int64_t* __restrict__ users, int64_t nrows, int64_t num_users, int64_t num_items,
-    const int64_t* __restrict__ mask_ptr, const int64_t* __restrict__ mask_idx, float mask_value,
-    const int64_t* __restrict__ hint, int k, float* __restrict__ row_tau) {
-  constexpr int G = 16, C = D / G, HPL = kEtMaxK / G;  // lane l owns hints l, l + 16, ...
+constexpr int kEtHintLanes = 16;                      // lanes per row of the hint kernels
+
+// What the two hint kernels (one table pair; NGCF's layer tables) share — everything but the dot product itself:
+// `dot(id, s, a)` adds this lane's share of the products of the row's user with item `id` to s and their absolute
+// values to a (id < 0: no item).  `row`: the lane group's row, `r` the row it reads (the last one beyond the input),
+// `margin`: et_hint_margin of the number of products per score.
+template <typename Dot>
+__device__ __forceinline__ void et_hint_bound(const float* __restrict__ item_bias, int64_t row, int64_t r, int64_t nrows,
+                                              bool user_ok, int64_t num_items, const int64_t* __restrict__ mask_ptr,
+                                              const int64_t* __restrict__ mask_idx, float mask_value,
+                                              const int64_t* __restrict__ hint, int k, float margin,
+                                              float* __restrict__ row_tau, Dot&& dot) {
+  constexpr int G = kEtHintLanes, HPL = kEtMaxK / G;   // lane l owns hints l, l + 16, ...
   const int l = threadIdx.x % G;
-  const int64_t row = (int64_t)blockIdx.x * (kBlock / G) + threadIdx.x / G;
-  const int64_t r = row < nrows ? row : nrows - 1;   // every lane group runs everything (shuffles below)
-  const int64_t uid = users[r];
-  const bool user_ok = (uint64_t)uid < (uint64_t)num_users;
-  constexpr bool WIDE = D > 128;                     // the user's row stays in memory, the dot product is a loop
-  float uu[WIDE ? 1 : C];
-  if constexpr (!WIDE) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) uu[c] = user_ok ? U[uid * D + C * l + c] : 0.0f;
-  }
   const int64_t m_lo = mask_ptr ? mask_ptr[r] : 0;
   const int len = mask_ptr ? (int)(mask_ptr[r + 1] - m_lo) : 0;
   const int64_t* mrow = mask_idx + m_lo;
@@ -204,6 +202,55 @@ __global__ __launch_bounds__(kBlock) void et_hint_bound_kernel(
 #pragma unroll
     for (int t = 0; t < HPL; ++t) fine = fine && !(j < l + G * t && l + G * t < k && idj == my[t]);
     float s = 0.0f, a = 0.0f;
+    dot(idj, s, a);
+#pragma unroll
+    for (int off = G / 2; off > 0; off >>= 1) {
+      s += __shfl_xor(s, off, G);
+      a += __shfl_xor(a, off, G);
+    }
+#pragma unroll
+    for (int t = 0; t < HPL; ++t)
+      if (l + G * t == j) { mys[t] = s; mya[t] = a; }
+  }
+  float eff = INFINITY;
+#pragma unroll
+  for (int t = 0; t < HPL; ++t) {
+    const float b = item_bias && my[t] >= 0 ? item_bias[my[t]] : 0.0f;
+    if (l + G * t < k) {
+      const float e = masked[t] ? mask_value : (mys[t] + b) - margin * (mya[t] + fabsf(b));
+      fine = fine && e == e;                         // a NaN score proves nothing (fminf would drop it silently)
+      eff = fminf(eff, e);
+    }
+  }
+  int all_fine = fine;                               // (taken after the NaN test above)
+#pragma unroll
+  for (int off = G / 2; off > 0; off >>= 1) {
+    eff = fminf(eff, __shfl_xor(eff, off, G));
+    all_fine &= __shfl_xor(all_fine, off, G);
+  }
+  if (row < nrows && l == 0) row_tau[row] = user_ok && k > 0 && all_fine ? eff : -INFINITY;
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void et_hint_bound_kernel(
+    const float* __restrict__ U, const float* __restrict__ I, const float* __restrict__ item_bias,
+    const int64_t* __restrict__ users, int64_t nrows, int64_t num_users, int64_t num_items,
+    const int64_t* __restrict__ mask_ptr, const int64_t* __restrict__ mask_idx, float mask_value,
+    const int64_t* __restrict__ hint, int k, float* __restrict__ row_tau) {
+  constexpr int G = kEtHintLanes, C = D / G;
+  const int l = threadIdx.x % G;
+  const int64_t row = (int64_t)blockIdx.x * (kBlock / G) + threadIdx.x / G;
+  const int64_t r = row < nrows ? row : nrows - 1;   // every lane group runs everything (shuffles in et_hint_bound)
+  const int64_t uid = users[r];
+  const bool user_ok = (uint64_t)uid < (uint64_t)num_users;
+  constexpr bool WIDE = D > 128;                     // the user's row stays in memory, the dot product is a loop
+  float uu[WIDE ? 1 : C];
+  if constexpr (!WIDE) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) uu[c] = user_ok ? U[uid * D + C * l + c] : 0.0f;
+  }
+  et_hint_bound(item_bias, row, r, nrows, user_ok, num_items, mask_ptr, mask_idx, mask_value, hint, k, et_hint_margin(D),
+                row_tau, [&](int idj, float& s, float& a) {
     if constexpr (WIDE) {
       if (idj >= 0 && user_ok) {
         const float* urow = U + uid * D + C * l;
@@ -224,32 +271,37 @@ __global__ __launch_bounds__(kBlock) void et_hint_bound_kernel(
         a += fabsf(x);
       }
     }
+  });
+}
+
+// The same bound for NGCF's score, the sum over the layer tables of per-layer dot products (ngcf_eval_topk_kernel):
+// lane l takes dims [l D / 16, (l + 1) D / 16) of every layer, layers ascending — n_layers D products per score, so
+// the margin is et_hint_margin(n_layers D).
+template <int D>
+__global__ __launch_bounds__(kBlock) void ngcf_hint_bound_kernel(
+    LayerPtrs L, int n_layers, const int64_t* __restrict__ users, int64_t nrows, int64_t num_users, int64_t num_items,
+    const int64_t* __restrict__ mask_ptr, const int64_t* __restrict__ mask_idx, float mask_value,
+    const int64_t* __restrict__ hint, int k, float* __restrict__ row_tau) {
+  constexpr int G = kEtHintLanes, C = D / G;
+  const int l = threadIdx.x % G;
+  const int64_t row = (int64_t)blockIdx.x * (kBlock / G) + threadIdx.x / G;
+  const int64_t r = row < nrows ? row : nrows - 1;
+  const int64_t uid = users[r];
+  const bool user_ok = (uint64_t)uid < (uint64_t)num_users;
+  et_hint_bound(nullptr, row, r, nrows, user_ok, num_items, mask_ptr, mask_idx, mask_value, hint, k,
+                et_hint_margin(n_layers * D), row_tau, [&](int idj, float& s, float& a) {
+    if (idj < 0 || !user_ok) return;
+    for (int ly = 0; ly < n_layers; ++ly) {
+      const float* urow = L.p[ly] + uid * D + C * l;
+      const float* irow = L.p[ly] + (num_users + idj) * D + C * l;
 #pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) {
-      s += __shfl_xor(s, off, G);
-      a += __shfl_xor(a, off, G);
+      for (int c = 0; c < C; ++c) {
+        const float x = urow[c] * irow[c];
+        s += x;
+        a += fabsf(x);
+      }
     }
-#pragma unroll
-    for (int t = 0; t < HPL; ++t)
-      if (l + G * t == j) { mys[t] = s; mya[t] = a; }
-  }
-  float eff = INFINITY;
-#pragma unroll
-  for (int t = 0; t < HPL; ++t) {
-    const float b = item_bias && my[t] >= 0 ? item_bias[my[t]] : 0.0f;
-    if (l + G * t < k) {
-      const float e = masked[t] ? mask_value : (mys[t] + b) - et_hint_margin(D) * (mya[t] + fabsf(b));
-      fine = fine && e == e;                         // a NaN score proves nothing (fminf would drop it silently)
-      eff = fminf(eff, e);
-    }
-  }
-  int all_fine = fine;                               // (taken after the NaN test above)
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) {
-    eff = fminf(eff, __shfl_xor(eff, off, G));
-    all_fine &= __shfl_xor(all_fine, off, G);
-  }
-  if (row < nrows && l == 0) row_tau[row] = user_ok && k > 0 && all_fine ? eff : -INFINITY;
+  });
 }
 
 // items per LDS stage: 64 where three workgroups per CU fit with it (f32; SPLIT at D <= 32), else 32 — except SPLIT
@@ -279,7 +331,8 @@ __host__ __device__ constexpr int et_chunk_items(int D, int KK, bool split) {
 // (Hint lists — et_hint_bound_kernel, row_tau — give a bound of the same kind from k rescored items instead.)
 // ---- pieces the three sweeps share (forceinline: lists, planes and accumulators stay in the callers' registers) ----
 // Three kernels sweep the catalogue — mf_eval_topk_kernel (four waves; also the prescan), mf_eval_topk_pp_kernel (two
-// roles per SIMD) and mf_eval_topk_wide_kernel (D = 256 / 512 / 1,024) — and must produce the same lists.  Each keeps
+// roles per SIMD) and mf_eval_topk_wide_kernel (D = 256 / 512 / 1,024) — and must produce the same lists; a fourth,
+// ngcf_eval_topk_kernel, sweeps NGCF's layer tables with the wide form's loop and the same pieces.  Each keeps
 // its own loops, staging and barriers; what happens to one tile is written ONCE, here: the user operand
 // (et_row_user, et_user_planes, et_user_half), the accumulator's start and the order of the products (et_start_acc,
 // et_products6, et_tile_split, et_tile_f32), the register -> item mapping (et_reg_item, et_set_where), the mask walk
@@ -1125,6 +1178,113 @@ __global__ __launch_bounds__(kEtThreads, 2) void mf_eval_topk_wide_kernel(
   et_finish_lists<KK>(Ls, Li, k, h, row, nrows, partial, out);
 }
 
+// ---- the sweep over LAYER TABLES (NGCF) -------------------------------------------------------------------------------
+// NGCF scores s(u, j) = sum_l E_l[u] . E_l[num_users + j] over its K + 1 layer buffers (csrc/ngcf.hip,
+// ngcf_score_kernel): a row of width W = n_layers D that exists in no table.  The wide form's slab loop with slab l
+// being LAYER l: per group of kEwTiles 32-item tiles, the group's item rows of E_l staged in LDS and each lane's half of
+// its user's row of E_l in registers, D dims per slab, the accumulators live across the layers — one f32 accumulator
+// per score, started at zero, the layers ascending and et_tile_f32's order inside a layer.  At D = 16 / 32 four / two
+// layers are staged per barrier pair (kept apart in LDS and in registers: the order of the products is the same).
+// Everything after the scores is the wide form's: mask cursor, et_collect, lockstep flush, hint thresholds
+// (ngcf_hint_bound_kernel), half-wave merge, catalogue slices by et_slices merged by mf_eval_merge_kernel.  f32 matrix
+// instruction only; no prescan.
+__host__ __device__ constexpr int ngcf_layers_per_stage(int D) { return D == 16 ? 4 : D == 32 ? 2 : 1; }
+
+template <int D, int KK>
+__global__ __launch_bounds__(kEtThreads, 2) void ngcf_eval_topk_kernel(
+    LayerPtrs L, int n_layers, const int64_t* __restrict__ users, int64_t nrows, int64_t num_users, int num_items,
+    const int64_t* __restrict__ mask_ptr, const int64_t* __restrict__ mask_idx, float mask_value, int k,
+    int64_t* __restrict__ out, TopEntry* __restrict__ partial, int items_per_slice, const float* __restrict__ row_tau,
+    int32_t* __restrict__ err_flag) {
+  static_assert(D == 16 || D == 32 || D == 64 || D == 128, "narrow widths only");
+  constexpr int LPS = ngcf_layers_per_stage(D), TILES = kEwTiles, MT = 32 * TILES;
+  constexpr int HALF = D / 2;                           // dims of a layer per lane
+  constexpr int ROWB = 4 * (D + 4);                     // an odd number of 16-byte units, as in the other forms
+  constexpr int ROW16 = D / 4;                          // 16-byte units per item row of a layer
+  constexpr int NV = MT * ROW16 / kEtThreads;
+  static_assert(MT * ROW16 % kEtThreads == 0, "units per thread");
+  constexpr int BUFCAP = kEtFlushAt + kEtCheckEvery;
+  __shared__ __attribute__((aligned(16))) unsigned char s_items[LPS][MT * ROWB];
+  __shared__ TopEntry s_buf[BUFCAP][kEtThreads];
+
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int i = lane & 31, h = lane >> 5;
+  const int64_t row = (int64_t)blockIdx.x * kEtUsers + wave * kEtUsersPerWave + i;
+  const int item_lo = blockIdx.y * items_per_slice;
+  const int item_hi = min(num_items, item_lo + items_per_slice);
+
+  int64_t uid;
+  const bool ok = et_row_user(users, row, nrows, num_users, err_flag, uid);
+  const int64_t uoff = (ok ? uid : 0) * D + h * HALF;   // this lane's half of its user's row, in every layer
+
+  float Ls[KK];
+  int32_t Li[KK];
+  const float tau0 = et_start_lists<KK>(Ls, Li, k, ok, row, row_tau, nullptr, 0);
+  float tau = fmaxf(Ls[KK - 1], tau0);
+  int cnt = 0;
+  const bool lazy_mask = mask_value <= -3.0e38f;     // uniform
+  EtMaskCursor masks(mask_ptr, mask_idx, row, nrows, item_lo);
+  auto flush = [&]() { et_flush(Ls, Li, s_buf, cnt, tau, tau0); };
+
+  // the MT item rows from c0 on of layer `ly`: global -> LDS stage j (zeros beyond the slice)
+  auto stage = [&](int c0, int ly, int j) {
+    const uint4* __restrict__ I16 = reinterpret_cast<const uint4*>(L.p[ly] + num_users * D);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int q = threadIdx.x + v * kEtThreads;
+      const int r = q / ROW16, c = q % ROW16;
+      uint4 x = make_uint4(0u, 0u, 0u, 0u);
+      if (c0 + r < item_hi) x = I16[(int64_t)(c0 + r) * ROW16 + c];
+      *reinterpret_cast<uint4*>(s_items[j] + r * ROWB + 16 * c) = x;
+    }
+  };
+
+  // mask, tail, threshold test and candidates of one tile
+  auto select = [&](f32x16& acc, int item0) {
+    const uint32_t bits = masks.walk<32>(item0);
+    const uint32_t mine = bits >> (4 * h);
+    if (!lazy_mask && __ballot(bits != 0) != 0ull) et_set_where(acc, mine, mask_value);
+    if (item0 + 32 > item_hi)                        // wave-uniform: last, partial tile of the slice: not items
+      et_set_where(acc, (~0u << (item_hi - item0)) >> (4 * h), -INFINITY);
+    et_collect<kEtCheckEvery>(acc, mine, item0 + 4 * h, lazy_mask, mask_value, row_tau != nullptr, tau, s_buf, cnt,
+                              flush);
+  };
+
+#pragma unroll 1
+  for (int c0 = item_lo; c0 < item_hi; c0 += MT) {
+    f32x16 acc[TILES];
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) acc[t] = zero16();
+#pragma unroll 1
+    for (int l0 = 0; l0 < n_layers; l0 += LPS) {
+      __syncthreads();                               // everyone is done reading the previous stages
+      float ub[LPS][HALF];                           // B operand: the user's half rows of layers l0 .. l0 + LPS - 1
+#pragma unroll
+      for (int j = 0; j < LPS; ++j) {
+        if (l0 + j < n_layers) {                     // uniform
+          stage(c0, l0 + j, j);
+          et_user_half<HALF>(L.p[l0 + j] + uoff, ok, ub[j]);
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < LPS; ++j) {
+        if (l0 + j < n_layers) {
+#pragma unroll
+          for (int t = 0; t < TILES; ++t)
+            et_tile_f32<HALF>(acc[t], reinterpret_cast<const float*>(s_items[j]) + (t * 32 + i) * (D + 4) + h * HALF,
+                              ub[j]);
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < TILES; ++t)
+      if (c0 + 32 * t < item_hi) select(acc[t], c0 + 32 * t);   // wave-uniform
+  }
+  flush();
+  et_finish_lists<KK>(Ls, Li, k, h, row, nrows, partial, out);
+}
+
 // out[r, :] = the k best of the S sorted partial lists of row r (score descending, item ascending
 // among equal scores; empty slots carry item 0x7fffffff and lose every comparison).  One thread per
 // row: S cursors, k rounds.
@@ -1426,6 +1586,93 @@ extern "C" int yr_mf_eval_topk(const float* U, const float* I, const int64_t* us
                                void* stream) {
   return yr_mf_eval_topk_bias(U, I, nullptr, users, nrows, D, num_users, num_items, mask_ptr, mask_idx, mask_value, k,
                               out, workspace, workspace_bytes, mode, hint, err_flag, stream);
+}
+
+// ---- NGCF: the sweep over the layer tables ----
+// the range checks both entry points make, before any pointer is read (0: fine)
+static int ngcf_et_check(int64_t nrows, int64_t num_items, int n_layers, int D, int k) {
+  if (nrows < 0 || num_items <= 0 || num_items > 0x7ffffff0 || n_layers < 1 || n_layers > YR_NGCF_MAX_LAYERS || k <= 0)
+    return YR_ERR_BADARG;
+  if (!(D == 16 || D == 32 || D == 64 || D == 128) || k > 16) return YR_ERR_UNSUPPORTED;
+  return 0;
+}
+
+extern "C" int64_t yr_ngcf_eval_topk_workspace_bytes(int64_t nrows, int64_t num_items, int n_layers, int D, int k) {
+  if (const int bad = ngcf_et_check(nrows, num_items, n_layers, D, k)) return bad;
+  if (nrows == 0) return 0;
+  const int S = et_slices(nrows, num_items);
+  return et_tau_bytes(nrows) + (S > 1 ? nrows * S * k * (int64_t)sizeof(TopEntry) : 0);
+}
+
+namespace {
+template <int DD, int KK, typename... A>
+void ngcf_et_run(dim3 grid, hipStream_t s, A... args) {
+  hipLaunchKernelGGL((ngcf_eval_topk_kernel<DD, KK>), grid, dim3(kEtThreads), 0, s, args...);
+}
+// the list length: the smallest of 4 / 10 / 16 entries that holds k
+template <int DD, typename... A>
+void ngcf_et_launch(int k, dim3 grid, hipStream_t s, A... args) {
+  if (k <= 4) ngcf_et_run<DD, 4>(grid, s, args...);
+  else if (k <= 10) ngcf_et_run<DD, 10>(grid, s, args...);
+  else ngcf_et_run<DD, 16>(grid, s, args...);
+}
+}  // namespace
+
+extern "C" int yr_ngcf_eval_topk(const float* const* layers, int n_layers, int D, const int64_t* users, int64_t nrows,
+                                 int64_t num_users, int64_t num_items, const int64_t* mask_ptr,
+                                 const int64_t* mask_idx, float mask_value, int k, int64_t* out, void* workspace,
+                                 int64_t workspace_bytes, const int64_t* hint, int32_t* err_flag, void* stream) {
+  if (num_users <= 0 || workspace_bytes < 0) return YR_ERR_BADARG;
+  if (const int bad = ngcf_et_check(nrows, num_items, n_layers, D, k)) return bad;
+  if (nrows == 0) return 0;
+  if (!layers || !users || !out || (mask_ptr && !mask_idx)) return YR_ERR_BADARG;
+  LayerPtrs L{};
+  for (int l = 0; l < n_layers; ++l) {
+    if (!layers[l]) return YR_ERR_BADARG;
+    L.p[l] = layers[l];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  if (!ws) workspace_bytes = 0;
+  const float* row_tau = nullptr;
+  if (hint && workspace_bytes >= et_tau_bytes(nrows)) {                       // no room: the hint is ignored
+    float* tau = reinterpret_cast<float*>(ws);
+    const dim3 hgrid((unsigned)((nrows + kBlock / kEtHintLanes - 1) / (kBlock / kEtHintLanes)));
+#define YR_NGCF_HINT(DD)                                                                                              \
+  hipLaunchKernelGGL((ngcf_hint_bound_kernel<DD>), hgrid, dim3(kBlock), 0, s, L, n_layers, users, nrows, num_users, \
+                     num_items, mask_ptr, mask_idx, mask_value, hint, k, tau)
+    switch (D) {
+      case 16: YR_NGCF_HINT(16); break;
+      case 32: YR_NGCF_HINT(32); break;
+      case 64: YR_NGCF_HINT(64); break;
+      default: YR_NGCF_HINT(128); break;
+    }
+#undef YR_NGCF_HINT
+    row_tau = tau;
+    ws += et_tau_bytes(nrows);
+    workspace_bytes -= et_tau_bytes(nrows);
+  }
+  int S = et_slices(nrows, num_items);
+  if (S > 1 && workspace_bytes < nrows * S * k * (int64_t)sizeof(TopEntry)) S = 1;          // no room: one slice
+  int per = (int)((num_items + S - 1) / S);
+  per = (per + 31) / 32 * 32;                          // whole 32-item tiles
+  S = (int)((num_items + per - 1) / per);
+  TopEntry* partial = S > 1 ? reinterpret_cast<TopEntry*>(ws) : nullptr;
+  const dim3 grid((unsigned)((nrows + kEtUsers - 1) / kEtUsers), (unsigned)S);
+#define YR_NGCF_SWEEP(DD)                                                                                           \
+  ngcf_et_launch<DD>(k, grid, s, L, n_layers, users, nrows, num_users, (int)num_items, mask_ptr, mask_idx, mask_value, \
+                     k, out, partial, per, row_tau, err_flag)
+  switch (D) {
+    case 16: YR_NGCF_SWEEP(16); break;
+    case 32: YR_NGCF_SWEEP(32); break;
+    case 64: YR_NGCF_SWEEP(64); break;
+    default: YR_NGCF_SWEEP(128); break;
+  }
+#undef YR_NGCF_SWEEP
+  if (S > 1)
+    hipLaunchKernelGGL(mf_eval_merge_kernel, dim3((unsigned)((nrows + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                       partial, nrows, S, k, out);
+  return launch_status();
 }
 
 #ifdef YR_PP_TRACE

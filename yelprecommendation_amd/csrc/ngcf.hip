@@ -205,7 +205,6 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_sliced_kernel(const int32_t* 
 // layers of per-layer dot products.  One launch scores positives and negatives over all layers
 // (one lane group per triplet, 16 bytes per lane, every layer's three rows in flight at once);
 // one launch scatter-adds the gradient of every layer buffer (float atomics, like index_add_).
-struct LayerPtrs { const float* p[YR_NGCF_MAX_LAYERS]; };
 struct LayerGradPtrs { float* p[YR_NGCF_MAX_LAYERS]; };
 
 __device__ __forceinline__ float dot4(const float4 a, const float4 b) {

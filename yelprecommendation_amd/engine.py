@@ -995,6 +995,50 @@ def mf_eval_topk(U, I, users, mask_ptr, mask_idx_sorted, k, mask_value=MASK_VALU
     return out
 
 
+def ngcf_eval_supports(k):
+    """The layered sweep (:func:`ngcf_eval_topk`) keeps lists of 4 / 10 / 16 entries in registers."""
+    return k <= 16
+
+
+def ngcf_eval_topk(layers, num_users, users, mask_ptr, mask_idx_sorted, k, mask_value=MASK_VALUE, out=None,
+                   sliced=True, hint=None):
+    """:func:`mf_eval_topk` for NGCF's score, the sum over the layer buffers of per-layer dot products (reference
+    models/ngcf.py:44-58 against the whole catalogue): ``layers`` = the K + 1 outputs of ``NGCF.propagate``, each
+    [num_users + num_items, D] with the users first.  One f32 accumulator per score over all (K + 1) D products on
+    the f32 matrix instruction; the layers are not concatenated and no score matrix is written.  ``mask_idx_sorted``,
+    ``sliced`` and ``hint`` as in :func:`mf_eval_topk`; k <= 16 (:func:`ngcf_eval_supports`)."""
+    lib = _lib.load()
+    ptrs = _ptr_array(layers, "layers")
+    n_all, d = layers[0].shape
+    if any(tuple(E.shape) != (n_all, d) for E in layers):
+        raise EngineError("layers must all be [num_users + num_items, D]")
+    ni = n_all - num_users
+    n = users.numel()
+    if mask_idx_sorted is not None and mask_idx_sorted.numel() == 0:
+        mask_ptr = mask_idx_sorted = None              # every list empty: an empty tensor has no address to pass
+    dev = layers[0].device
+    if out is None:
+        out = torch.empty((n, k), dtype=torch.int64, device=dev)
+    if hint is not None and tuple(hint.shape) != (n, k):
+        raise EngineError(f"hint must be [{n}, {k}] item ids, got {tuple(hint.shape)}")
+    flag = new_error_flag(dev)
+    if sliced:
+        ws_bytes = lib.yr_ngcf_eval_topk_workspace_bytes(n, ni, len(layers), d, int(k))
+    else:
+        ws_bytes = -(-n * 4 // 256) * 256 if hint is not None else 0
+    if ws_bytes < 0:
+        check(int(ws_bytes), "yr_ngcf_eval_topk_workspace_bytes")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    check(lib.yr_ngcf_eval_topk(ptrs, len(layers), d, _dev(users, torch.int64, "users"), n,
+                                int(num_users), ni, _opt(mask_ptr, torch.int64, "mask_ptr"),
+                                _opt(mask_idx_sorted, torch.int64, "mask_idx"), float(mask_value), int(k),
+                                _dev(out, torch.int64, "out"), ws.data_ptr() if ws is not None else None, ws_bytes,
+                                _opt(hint, torch.int64, "hint"), flag.data_ptr(), _stream()),
+          "yr_ngcf_eval_topk")
+    raise_on_flag(flag, "ngcf_eval_topk")
+    return out
+
+
 def mf_recommend(U, I, users, mask_ptr, mask_idx, k, chunk_users=4096, fused=None):
     """Top-k unmasked items for each user id in ``users`` (reference
     trainers/mf_trainer.py:134-144 + :163-178, batched), all on the device.

@@ -7,6 +7,7 @@ the reference's layout (or the built-in defaults) plus ``key=value`` overrides.
     python -m yelprecommendation_amd.train model_name=DCN synthetic=yelp2018 fast_loader=true hidden_dims=[64,32]
     python -m yelprecommendation_amd.train model_name=S3Rec synthetic=yelp2018 fast_loader=true batch_size=256
     python -m yelprecommendation_amd.train model_name=S3Rec synthetic=yelp2018 fast_loader=true full_eval=true
+    python -m yelprecommendation_amd.train model_name=NGCF synthetic=yelp2018 fast_loader=true full_eval=true
 
 Call order is the reference's: pipeline.preprocess() -> split() -> datasets -> set_seed() ->
 DataLoaders -> trainer.run() -> load_best_model() -> evaluate(test).

@@ -108,20 +108,26 @@ class BaseTrainer(ABC):
         cnt, ps, rs, ms, ns, total = sums.tolist()                 # the one read-back
         return (ps / total, rs / cnt, ms / cnt, ns / cnt)
 
-    def _hinted_topk(self, key, U, I, users, mask_ptr, mask_idx, **kw):
-        """engine.mf_eval_topk under cfg.eval_precision ("bf16x3", the default: f32 scores from three-term bf16
-        splits, or "f32").  Evaluations under the same ``key`` hand their result to the next one as hint lists (the
-        lists start from the smallest score among a user's previous top-n under the CURRENT model — a bound the
-        result cannot depend on); ``key`` None or cfg.eval_hints=False turns that off."""
+    def _with_hints(self, key, nrows, topk):
+        """``topk(hint)`` — a fused evaluation of ``nrows`` rows — with the hint lists kept under ``key``:
+        evaluations under the same key hand their result to the next one (the lists start from the smallest score
+        among a user's previous top-n under the CURRENT model — a bound the result cannot depend on); ``key`` None or
+        cfg.eval_hints=False turns that off."""
         hinted = key is not None and self.cfg.get("eval_hints", True)
         hint = self._eval_hints.get(key) if hinted else None
-        if hint is not None and tuple(hint.shape) != (users.numel(), self.cfg.top_n):
+        if hint is not None and tuple(hint.shape) != (nrows, self.cfg.top_n):
             hint = None
-        top = engine.mf_eval_topk(U, I, users, mask_ptr, mask_idx, self.cfg.top_n,
-                                  precision=self.cfg.get("eval_precision", "bf16x3"), hint=hint, **kw)
+        top = topk(hint)
         if hinted:
             self._eval_hints[key] = top
         return top
+
+    def _hinted_topk(self, key, U, I, users, mask_ptr, mask_idx, **kw):
+        """engine.mf_eval_topk under cfg.eval_precision ("bf16x3", the default: f32 scores from three-term bf16
+        splits, or "f32"), with hint lists per ``key`` (:meth:`_with_hints`)."""
+        return self._with_hints(key, users.numel(), lambda hint: engine.mf_eval_topk(
+            U, I, users, mask_ptr, mask_idx, self.cfg.top_n, precision=self.cfg.get("eval_precision", "bf16x3"),
+            hint=hint, **kw))
 
     def _is_surpass_best_metric(self, **metric) -> bool:
         """``current`` beats ``best`` on ``cfg.best_metric`` (both are (valid_loss, precision, recall,

@@ -7,6 +7,13 @@ NumPy RNG exactly like the reference (ngcf_trainer.py:140) — but propagates th
 call instead of once per sampled user.  With Adam / AdamW ``train`` runs every batch as ONE engine call
 (ngcf_step.NGCFStep: the launches of the autograd route, issued from C; cfg.fused_step=False keeps the reference's
 loop shape — bpr_forward, zero_grad, loss, backward, step — on the HIP autograd ops).
+
+Full-catalogue evaluation (new; the reference has only the 100-row sample): ``evaluate_full`` ranks the whole
+catalogue for EVERY row of the eval frame — one propagation, then the fused sweep over the layer tables
+(engine.ngcf_eval_topk: no score matrix, the layers not concatenated) and the metrics on the device, as MF, CDAE and
+DCN evaluate.  ``cfg.full_eval=true`` makes ``evaluate`` delegate to it in both modes, so ``run`` selects its best
+model on all users and draws nothing from NumPy's global RNG; false or absent, ``evaluate`` is the reference's sample,
+including its one ``np.random.randint(len(eval_data), size=100)`` draw.
 """
 import numpy as np
 import torch
@@ -16,7 +23,7 @@ from ..metric import ranking_metrics
 from ..models.ngcf import NGCF, _iadd
 from ..utils import logger
 from .base_trainer import TripletTrainer
-from .eval_set import _lists_to_csr, top_k_of_scores
+from .eval_set import EvalSets, _lists_to_csr, top_k_of_scores
 
 
 class NGCFTrainer(TripletTrainer):
@@ -29,6 +36,7 @@ class NGCFTrainer(TripletTrainer):
         self.optimizer = self._optimizer(self.cfg.optimizer, self.model, self.cfg.lr, self.cfg.weight_decay)
         self.loss = self._loss()
         self.laplacian_matrix = laplacian_matrix
+        self._eval_sets = EvalSets(self.device)
 
     def _fused_step(self):
         """The whole batch step as one engine call (ngcf_step.NGCFStep) for Adam / AdamW unless
@@ -87,19 +95,70 @@ class NGCFTrainer(TripletTrainer):
         self.model.check_indices()
         return float(self._loss_accum.item())
 
-    def recommend(self, users, mask_ptr, mask_idx):
+    def recommend(self, users, mask_ptr, mask_idx, fused=False, hint_key=None):
         """Top-``top_n`` unmasked items for the given user ids ([n, top_n] int64 on the device):
-        one propagation, then S = sum_k E_k[users] E_k[items]^T on the matrix cores, mask, top-k."""
+        one propagation, then S = sum_k E_k[users] E_k[items]^T on the matrix cores, mask, top-k.
+        ``fused``: the sweep over the layer tables instead (engine.ngcf_eval_topk: scores, mask and top-k in one
+        kernel, no [n, num_items] matrix; top_n <= 16; the mask lists must be sorted ascending inside each row).
+        ``hint_key``: fused evaluations under the same key hand their result to the next one as hint lists
+        (BaseTrainer._with_hints; cfg.eval_hints=False turns it off)."""
         layers = self.model.propagate(self.laplacian_matrix)
         nu = self.num_users
+        if fused:
+            users = users.contiguous()
+            return self._with_hints(hint_key, users.numel(), lambda hint: engine.ngcf_eval_topk(
+                layers, nu, users, mask_ptr, mask_idx, self.cfg.top_n, hint=hint))
         scores = None
         for E in layers:
             s = engine.mf_scores_gemm(E[:nu], E[nu:], users)
             scores = s if scores is None else _iadd(scores, s)
         return engine.topk_masked(scores, mask_ptr, mask_idx, self.cfg.top_n)
 
+    # rows per chunk of the dense route of evaluate_full: two score buffers of this many rows, 4,096 x num_items
+    # floats in all (0.62 GB at Yelp2018 size)
+    full_eval_chunk_users = 2048
+
+    def _recommend_chunked(self, users, mask_ptr, mask_idx):
+        """:meth:`recommend`'s dense route for any number of users: one propagation, then chunk after chunk of
+        ``full_eval_chunk_users`` rows through the same two score buffers — never an [all users, items] array."""
+        layers = self.model.propagate(self.laplacian_matrix)
+        nu, n = self.num_users, users.numel()
+        rows = max(1, min(int(self.full_eval_chunk_users), n))
+        bufs = [torch.empty((rows, self.num_items), dtype=torch.float32, device=self.device) for _ in range(2)]
+        out = torch.empty((n, self.cfg.top_n), dtype=torch.int64, device=self.device)
+        mask_rows = torch.arange(n, dtype=torch.int64, device=self.device)
+        flag = self.model._flag()
+        for lo in range(0, n, rows):
+            hi = min(lo + rows, n)
+            chunk = users[lo:hi].contiguous()
+            scores = engine.mf_scores_gemm(layers[0][:nu], layers[0][nu:], chunk, out=bufs[0], err_flag=flag)
+            for E in layers[1:]:
+                _iadd(scores, engine.mf_scores_gemm(E[:nu], E[nu:], chunk, out=bufs[1], err_flag=flag))
+            engine.topk_masked(scores, mask_ptr, mask_idx, self.cfg.top_n, out=out[lo:hi], mask_rows=mask_rows[lo:hi])
+        self.model.check_indices()
+        return out
+
+    def evaluate_full(self, eval_data, mode='valid') -> tuple:
+        """(precision, recall, map, ndcg)@top_n over ALL rows of ``eval_data`` (a frame indexed by user id with list
+        columns 'pos_items' and 'mask_items'), the whole catalogue ranked for each: the fused sweep over the layer
+        tables up to top_n = 16, beyond it the dense route in chunks of users (:meth:`_recommend_chunked`).  The
+        lists stay in ``last_full_topk`` ([rows, top_n] int64 on the device, in the frame's row order)."""
+        self.model.eval()
+        users, mask_ptr, mask_idx, pos_ptr, pos_idx = self._eval_sets.eval_set(eval_data, sort_masks=True)[2:7]
+        if engine.ngcf_eval_supports(self.cfg.top_n):
+            predicted = self.recommend(users, mask_ptr, mask_idx, fused=True, hint_key=id(eval_data))
+        else:
+            predicted = self._recommend_chunked(users, mask_ptr, mask_idx)
+        self.last_full_topk = predicted
+        p, r, m, n = engine.rank_metrics(predicted, pos_ptr, pos_idx)[:4].tolist()
+        if mode == 'test':
+            self._log_test(p, r, m, n)
+        return (p, r, m, n)
+
     def evaluate(self, eval_data, mode='valid') -> tuple:
         # reference ngcf_trainer.py:134-165
+        if self.cfg.get("full_eval", False):
+            return self.evaluate_full(eval_data, mode)
         self.model.eval()
         positions = np.random.randint(eval_data.shape[0], size=100)            # :140, global NumPy RNG
         users = np.asarray(eval_data.index.values, dtype=np.int64)[positions]

@@ -54,6 +54,9 @@ DEFAULTS = Config(
     data_dir="data/", log_dir="logs/", sweep=False, wandb=False,
     device="cuda", epochs=5, batch_size=32, lr=1e-4, optimizer="adam", loss_name="bpr",
     patience=5, top_n=10, weight_decay=0, best_metric="loss", model_name="MF",
+    # not in the reference: evaluate against the whole catalogue for every eval row — NGCF: evaluate() delegates to
+    # evaluate_full() (all users instead of 100 sampled rows); S3Rec: evaluate_full() after the test evaluation
+    full_eval=False,
     model=dict(
         CDAE=dict(negative_sampling=True, neg_times=5, hidden_size=64, corruption_level=0.6,
                   hidden_activation="sigmoid", output_activation="sigmoid"),
