@@ -753,7 +753,37 @@ int yr_cdae_hidden_bwd_dwh_t(const int32_t *cols, const float *vals, const int32
                              double *loss_accum, void *stream);
 
 /* ---------------------------------------------------------------------------
- * Device-side BPR triplet stream   (reference train.py:76-77: DataLoader(MFDataset, shuffle=True);
+ * CDAE without negative sampling: catalogue BCE   (reference trainers/cdae_trainer.py:36-54 with
+ *   negative_sampling: false — loss.py's BCELoss, nn.BCELoss, on the [B, I] prediction of models/cdae.py:46-52 against
+ *   the dense [B, I] input rows, mean over all elements; csrc/cdae_catalogue.hip)
+ * z [B][H] (the hidden rows) against every row of W_o [I][H] with the bias b_o [I], z and W_o 16-byte aligned:
+ *     pre[n, i] = <z[n], W_o[i]> + b_o[i]      y = act(pre)  (act 1: sigmoid, 0: identity)      t = [i in targets(user[n])]
+ *     row_loss[n] = sum_i -( t max(log y, -100) + (1 - t) max(log(1 - y), -100) )          (NOT divided by B I)
+ *     g[n, i] = (y - t) / max((1 - y) y, 1e-12) act'(y) / (B I)       dz = g W_o      dW_o = g^T z      db_o = sum_n g
+ * — the term and the gradient of yr_cdae_decode_loss with negative_mask = null, f32 saturation included (this is BCE on
+ * the prediction, not BCE-with-logits).  The three gradients carry the mean's 1 / (B I): their consumers do not scale.
+ * user [B]: the key of a row; its targets are tgt_idx[tgt_ptr[user] .. tgt_ptr[user + 1]) (a CSR over K users, item
+ * ids ascending and duplicate-free inside a user).  A key outside [0, K) raises YR_FLAG_BAD_ITEM and counts as a row
+ * without targets; a target outside [0, I) is no column.
+ * row_loss [B] is required.  dz may be null; dW_o and db_o come together or are both null (all three null: the
+ * loss-only call, which writes no gradient).  All outputs are overwritten, not accumulated.  No [B][I] array is
+ * written in any pass: the pass that owns rows of z takes the loss and dz, the pass that owns rows of W_o computes the
+ * pre-activations again for dW_o and db_o.  No float atomics: the column sums of a row run over chunks of 2,048
+ * columns in a fixed order (a row's row_loss and dz do not depend on B, except through the factor 1 / (B I) of dz),
+ * dW_o's and db_o's row sums over the 32-row tiles dealt to four waves; two calls give one answer bit for bit.
+ * workspace: yr_cdae_catalogue_bce_workspace_floats(B, I, H) floats (a negative YR_ERR_* for refused sizes), any
+ * contents; the call without dz needs B ceil(I / 2,048) of them.  Checked before any launch: negative sizes, H <= 0, an
+ * act other than 0 / 1: YR_ERR_BADARG; a width outside 16 / 32 / 64 / 128: YR_ERR_UNSUPPORTED; then B == 0 or I == 0:
+ * 0 (nothing is written); then null or misaligned pointers, dW_o without db_o, a workspace too small: YR_ERR_BADARG.
+ * ------------------------------------------------------------------------- */
+int64_t yr_cdae_catalogue_bce_workspace_floats(int64_t B, int64_t I, int H);
+int yr_cdae_catalogue_bce(const float *z, const float *Wo, const float *bo, const int64_t *user,
+                          const int64_t *tgt_ptr, const int64_t *tgt_idx, int64_t B, int64_t I, int64_t K, int H,
+                          int act, float *row_loss, float *dz, float *dWo, float *dbo, float *workspace,
+                          int64_t workspace_floats, int32_t *err_flag, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Device-side BPR triplet stream  (reference train.py:76-77: DataLoader(MFDataset, shuffle=True);
  *   data/datasets/mf_dataset.py:18-32: __getitem__ + _negative_sampling)
  * Stream positions [first, first + count) of epoch `epoch`: position t reads row P(t) of
  * (row_user, row_item) — P a keyed pseudo-random permutation of [0, n_rows) when `shuffle`, the

@@ -85,6 +85,14 @@ BUDGETS = [
      "four waves per SIMD (512 / 4 -> 128): more than the two workgroups per CU of the cbce kernel; no scratch"),
     (r"void yr::s3rec_rank_kernel<128>", 256, 1024, "as above at E = 128: 64 row registers, two waves per SIMD"),
     (r"yr::s3rec_rank_sum_kernel", 64, 0, "streaming integer sums of the chunks' counts"),
+    # CDAE without negative sampling: the catalogue BCE on the geometry of s3rec_cbce_kernel
+    (r"void yr::cdae_cbce_kernel<(16|32|64), (true|false)>", 256, 9 * 1024,
+     "CDAE plain BCE, catalogue sweep: the owned rows (H / 2 registers), their gradient (H / 2) and one tile of "
+     "pre-activations, with expf / logf / the division of the dense decoder's epilogue; two workgroups per CU = two "
+     "waves per SIMD (512 / 2 -> 256; 230 at H = 64 owning rows); no scratch"),
+    (r"void yr::cdae_cbce_kernel<128, (true|false)>", 512, 17 * 1024,
+     "as above at H = 128: 64 + 64 row registers, one wave per SIMD; 16.1 KB of LDS for the wave-order sum; no scratch"),
+    (r"yr::cdae_cbce_reduce_kernel", 64, 0, "streaming sums of the chunks' partials in a fixed order"),
 ]
 # Scratch (spilled registers) per lane.  The forms the benchmark and the trainers run by default — width 64, summation
 # order free — must have none; the deterministic-order forms and some forms of the other widths are held at 64 VGPRs by

@@ -31,6 +31,12 @@ decoder products are gone.  Validation / evaluation still decode the whole catal
 Adam launch clears what it read — for dV only the rows the batch touched), dW_o / db_o / db_h are
 overwritten whole.  Results equal the autograd route (models/cdae.py + loss.py + optim.py) up to float
 rounding: the 1 / count factor is applied to the products instead of to G.
+
+Without negative sampling the loss reads every catalogue position (loss.py's BCELoss).  On dense batches (``step``)
+that is the dense decoder above.  On list batches (``step_lists``, hidden size 16 / 32 / 64 / 128) steps 3-6 are one
+call, yr_cdae_catalogue_bce (csrc/cdae_catalogue.hip): the targets are the per-user item lists, the loss is taken in
+the epilogue of a matrix sweep and the pre-activations are computed again for dW_o / db_o — no [B, I] array, no float
+atomics, dz / dW_o / db_o final (1 / (B I) applied in the kernel) and each written whole.
 """
 import torch
 
@@ -75,6 +81,9 @@ class CDAEStep:
         if decoder not in ("sampled", "dense") or (decoder == "sampled" and not can_sample):
             raise NotImplementedError(f"CDAEStep: decoder {decoder!r} with negative_sampling={negative_sampling}, H={H}")
         self.decoder = decoder
+        # plain BCE on list batches: the catalogue sweep (csrc/cdae_catalogue.hip) in place of the dense decoder
+        self.catalogue = not self.negative_sampling and self.row_marks and H in engine.CDAE_CATALOGUE_HIDDEN
+        self._cat = None                               # (B, row_loss, spread count B I, workspace) of step_lists
         self.transposed_wh = bool(transposed_wh) and self.row_marks
         self._wht = None                               # (WhT, mT, vT, dWhT, item marks) while acquired
         dev = self.params[0].device
@@ -142,8 +151,7 @@ class CDAEStep:
             if self.decoder == "sampled":
                 self.n_partials = B * engine.cdae_sampled_decode_splits(B)
             else:
-                ldg = (I + 3) // 4 * 4                                            # 16-byte rows: the gradient products
-                self.G = torch.empty(B, ldg, dtype=f32, device=dev)[:, :I]       # that read G take the tiled kernel
+                self.G = None                             # [B, I]: made by the first dense batch (step_lists needs none)
                 self.n_partials = engine.cdae_decode_loss_partials(B, I)
             self.partials = torch.empty(self.n_partials, dtype=f32, device=dev)
             self._batch = B
@@ -183,19 +191,36 @@ class CDAEStep:
     def step_lists(self, user_id, lists):
         """One training step on a batch that arrives as lists (engine.TrainLists from data/cdae_batches.py:
         encoder input and loss positions straight from the per-user CSR — no dense row, no dense mask, no
-        compaction pass).  Sampled decoder only."""
-        if self.decoder != "sampled":
+        compaction pass).  With NS-BCE: the sampled decoder on the lists' loss positions.  With plain BCE
+        (``negative_sampling=False``, hidden size 16 / 32 / 64 / 128): the loss runs over every catalogue position, its
+        targets are ``lists.targets`` — the per-user CSR the batch belongs to (CDAEBatchLoader(negative_sampling=False)
+        attaches it) — and the catalogue sweep yr_cdae_catalogue_bce stands where ``step`` runs the three dense decoder
+        launches: no [B, I] array, dz / dW_o / db_o final (the mean's 1 / (B I) applied in the kernel)."""
+        if self.decoder != "sampled" and not self.catalogue:
             raise NotImplementedError("step_lists needs the sampled decoder (NS-BCE)")
         if lists.B == 0:
             return
         lists.alive()
         self._buffers(lists.B)
-        self._run(user_id.contiguous(), lists.rows, lists.loss, None, None)
+        if self.decoder == "sampled":
+            self._run(user_id.contiguous(), lists.rows, lists.loss, None, None)
+            return
+        if getattr(lists, "targets", None) is None:
+            raise engine.EngineError("step_lists under plain BCE needs the batch's target CSR (lists.targets)")
+        if self._cat is None or self._cat[0] != lists.B:
+            H, I = self.params[0].shape
+            dev = self.params[0].device
+            self._cat = (lists.B, torch.empty(lists.B, dtype=torch.float32, device=dev),
+                         engine.spread_count(lists.B * I, dev),
+                         torch.empty(engine.cdae_catalogue_bce_workspace_floats(lists.B, I, H), dtype=torch.float32,
+                                     device=dev))
+        self._run(user_id.contiguous(), lists.rows, None, None, None, targets=lists.targets)
 
-    def _run(self, user_id, rows, loss_lists, x, neg):
+    def _run(self, user_id, rows, loss_lists, x, neg, targets=None):
         model = self.model
         Wh, bh, V, Wo, bo = (q.data for q in self.params)
         sampled = loss_lists is not None
+        partials, n_partials, count = self.partials, self.n_partials, self.count
         self.acquire()
         wt = self._wht
         if wt is not None:
@@ -203,11 +228,24 @@ class CDAEStep:
                                       transposed=True)
         else:
             engine.cdae_sparse_encode(rows, Wh, bh, V, user_id, model._hidden_act, err_flag=self.flag, out=self.z)
-        self._blob.zero_()
-        if sampled:
+        if targets is not None:
+            # every position of the catalogue: loss and the three decoder gradients from two sweeps, each output
+            # written whole (nothing to clear); the rows' loss sums are the partials, B I their count
+            _, partials, count, workspace = self._cat
+            n_partials = partials.numel()
+            engine.cdae_catalogue_bce(self.z, Wo, bo, user_id, targets[0], targets[1], model._output_act,
+                                      workspace=workspace, err_flag=self.flag,
+                                      out=(partials, self.dz, self.dWo, self.dbo))
+        elif sampled:
+            self._blob.zero_()
             engine.cdae_sampled_decode(loss_lists, self.z, Wo, bo, model._output_act, self.dz, self.dWo,
                                        self.dbo, self.partials, self.count)
         else:
+            if self.G is None:
+                B, I = x.shape
+                ldg = (I + 3) // 4 * 4                                            # 16-byte rows: the gradient products
+                self.G = torch.empty(B, ldg, dtype=torch.float32, device=x.device)[:, :I]   # that read G take the tiled kernel
+            self._blob.zero_()
             engine.cdae_decode_loss(self.z, Wo, bo, x, neg, model._output_act, self.G, self.partials, self.count)
             engine.gemm_f32(self.G, self.z, transA=True, out=self.dWo, alpha_count=self.count, rowsum=self.dbo)
             engine.gemm_f32(self.G, Wo, out=self.dz, accumulate=True, split_k=max(1, min(256, Wo.shape[0] // 256)),
@@ -215,13 +253,12 @@ class CDAEStep:
         if wt is not None and self.hidden_size <= 1024:
             # hidden layer's backward, db_h, dV, dW_h^T and the step's loss in one launch (db_h accumulates: the
             # Adam launch clears it)
-            engine.cdae_hidden_bwd_dwh_t(rows, self.dz, self.z, model._hidden_act, user_id, self.count, self.dV,
-                                         self.touched_users, self.dbh, wt[3], wt[4], self.partials, self.n_partials,
+            engine.cdae_hidden_bwd_dwh_t(rows, self.dz, self.z, model._hidden_act, user_id, count, self.dV,
+                                         self.touched_users, self.dbh, wt[3], wt[4], partials, n_partials,
                                          self.stats, self.loss_accum, scale_dz=sampled)
         else:
             engine.cdae_hidden_bwd(self.dz, self.z, model._hidden_act, user_id, self.dV, self.touched_users, self.dbh,
-                                   self.partials, self.n_partials, self.count, self.stats, self.loss_accum,
-                                   scale_dz=sampled)
+                                   partials, n_partials, count, self.stats, self.loss_accum, scale_dz=sampled)
             if wt is not None:
                 engine.cdae_sparse_dwh_t(rows, self.dz, wt[3], wt[4])
             else:

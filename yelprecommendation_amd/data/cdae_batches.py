@@ -125,18 +125,22 @@ class CDAEBatchLoader:
     """
 
     def __init__(self, data: CDAEInteractions, mode="train", batch_size=32, neg_times=5, shuffle=False, seed=0,
-                 lists=False, dropout=0.0):
+                 lists=False, dropout=0.0, negative_sampling=True):
         """``lists=True``: a batch is ``{"user_id", "lists"[, "item_lists"]}`` with ``lists`` an engine.TrainLists —
         the encoder's input and the NS-BCE positions (positives + ``neg_times`` x as many sampled negatives) as
         per-row lists made straight from the CSR (yr_cdae_train_lists); no dense row or mask exists.
         'train': input = train items after nn.Dropout(``dropout``), positives = train items (CDAETrainer.train feeds
         the fused step); 'valid': input = train items, positives = train + held-out items; 'test': input = train +
         valid items, no loss list.  CDAETrainer.validate / evaluate then score all users at once with the fused
-        evaluation kernel."""
+        evaluation kernel.
+        ``negative_sampling=False`` with ``lists=True`` (plain BCE over every catalogue position): no negatives are
+        drawn (the loss list holds the positives only and nobody reads it) and every batch's ``lists.targets`` is the
+        per-user CSR its loss reads — 'train' for training, 'train_valid' for validation — for the catalogue sweep
+        (engine.cdae_catalogue_bce).  Dense batches are what they are with the default."""
         if mode not in ("train", "valid", "test"):
             raise ValueError(f"mode {mode!r}")
         self.data, self.mode, self.batch_size, self.neg_times, self.shuffle = data, mode, int(batch_size), neg_times, shuffle
-        self.lists, self.dropout = bool(lists), float(dropout)
+        self.lists, self.dropout, self.negative_sampling = bool(lists), float(dropout), bool(negative_sampling)
         self._gen = torch.Generator(device=data.device).manual_seed(seed)
         self._seeds = torch.Generator().manual_seed(seed)          # host generator: per-batch kernel seeds
         self._flag = engine.new_error_flag(data.device) if data.device.type == "cuda" else None   # cpu store: iterating raises
@@ -150,6 +154,15 @@ class CDAEBatchLoader:
         items with the smallest of I i.i.d. random keys among the non-positives."""
         seed = int(torch.randint(0, 1 << 62, (1,), generator=self._seeds).item())
         return engine.negative_mask(positives.contiguous(), self.neg_times, seed, err_flag=self._flag)
+
+    def _list_neg_times(self):
+        return 0 if self.mode == "test" or not self.negative_sampling else self.neg_times
+
+    def _list_targets(self):
+        """The target CSR of a plain-BCE list batch (None with NS-BCE and for the 'test' loader: no loss there)."""
+        if self.negative_sampling or self.mode == "test":
+            return None
+        return self.data.csr("train" if self.mode == "train" else "train_valid")
 
     def super_batches(self, group=8):
         """lists=True, mode 'valid' / 'test': the same batches, ``group`` at a time — ``{"user_id" (all rows of the
@@ -172,10 +185,10 @@ class CDAEBatchLoader:
             seeds = torch.randint(0, 1 << 62, (nb, 2), generator=self._seeds)      # the draws of nb single batches
             seeds = seeds.to(d.device)
             ptr, idx = d.csr("train_valid" if self.mode == "test" else "train")
-            made = engine.TrainLists(ptr, idx, users, d.num_users, d.num_items, 0 if self.mode == "test" else self.neg_times,
+            made = engine.TrainLists(ptr, idx, users, d.num_users, d.num_items, self._list_neg_times(),
                                      seeds[:, 0].contiguous(), seeds[:, 1].contiguous(), 0.0, err_flag=self._flag,
                                      extra=d.csr("valid") if self.mode == "valid" else None, pool=self._list_pool,
-                                     batch_rows=bs)
+                                     batch_rows=bs, targets=self._list_targets())
             yield {"user_id": users, "lists": made, "batch_rows": bs, "item_lists": dict(lists, users=users)}
         if self._flag is not None and int(self._flag.item()):
             self._flag.zero_()
@@ -198,9 +211,10 @@ class CDAEBatchLoader:
                 seeds = torch.randint(0, 1 << 62, (2,), generator=self._seeds).tolist()
                 ptr, idx = d.csr("train_valid" if self.mode == "test" else "train")
                 made = engine.TrainLists(ptr, idx, users.contiguous(), d.num_users, d.num_items,
-                                         0 if self.mode == "test" else self.neg_times, seeds[0], seeds[1],
+                                         self._list_neg_times(), seeds[0], seeds[1],
                                          self.dropout if self.mode == "train" else 0.0, err_flag=self._flag,
-                                         extra=d.csr("valid") if self.mode == "valid" else None, pool=self._list_pool)
+                                         extra=d.csr("valid") if self.mode == "valid" else None, pool=self._list_pool,
+                                         targets=self._list_targets())
                 batch = {"user_id": users, "lists": made}
                 if self.mode != "train":
                     batch["item_lists"] = lists

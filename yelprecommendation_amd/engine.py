@@ -533,12 +533,14 @@ class TrainLists:
     _pool = {}
 
     def __init__(self, ptr, idx, users, num_users, num_items, neg_times, neg_seed, drop_seed, p, err_flag=None,
-                 extra=None, pool=None, batch_rows=None):
+                 extra=None, pool=None, batch_rows=None, targets=None):
         """``extra``: (ptr, idx) of a second per-user CSR whose items are positives of the loss list too (the
         held-out items in validation) without entering the encoder list.
         ``batch_rows``: ``users`` holds SEVERAL batches of that many rows (the last may be short) and ``neg_seed`` /
         ``drop_seed`` are int64 device tensors with one seed per batch — one launch makes exactly the lists one
-        TrainLists per batch would (yr_cdae_train_lists_batched)."""
+        TrainLists per batch would (yr_cdae_train_lists_batched).
+        ``targets``: (ptr, idx) of the per-user CSR the plain-BCE loss of these rows reads (cdae_catalogue_bce: every
+        catalogue position, no loss list); kept as ``self.targets`` beside the lists, not read here."""
         lib = _lib.load()
         B, I = users.numel(), int(num_items)
         dev = users.device
@@ -577,6 +579,7 @@ class TrainLists:
                                           _opt(err_flag, torch.int32, "err_flag"), _stream()), "yr_cdae_train_lists")
         self.rows = SparseRows.from_buffers(buf[0], buf[1], buf[2], B, I)
         self.loss = (buf[3], buf[4], buf[5])
+        self.targets = targets
         self.B, self.I = B, I
 
     def alive(self):
@@ -613,6 +616,65 @@ def cdae_sampled_decode(loss_lists, z, Wo, bo, act, dz, dWo, dbo, partial_loss, 
                                      _opt(bo, f32, "bo"), B, I, H, int(act), _opt(dz, f32, "dz"), _opt(dWo, f32, "dWo"),
                                      _opt(dbo, f32, "dbo"), _dev(partial_loss, f32, "partial_loss"), _dev(count, torch.int32, "count"),
                                      _stream()), "yr_cdae_sampled_decode")
+
+
+# ---- CDAE without negative sampling (csrc/cdae_catalogue.hip: the catalogue BCE) ----
+CDAE_CATALOGUE_HIDDEN = (16, 32, 64, 128)      # the widths yr_cdae_catalogue_bce is built for
+
+
+def cdae_catalogue_bce_workspace_floats(B, I, H):
+    """Floats of the catalogue-BCE workspace (yr_cdae_catalogue_bce_workspace_floats)."""
+    n = _lib.load().yr_cdae_catalogue_bce_workspace_floats(int(B), int(I), int(H))
+    if n < 0:
+        check(int(n), "yr_cdae_catalogue_bce_workspace_floats")
+    return int(n)
+
+
+def cdae_catalogue_bce(z, Wo, bo, users, tgt_ptr, tgt_idx, act, grads=True, workspace=None, err_flag=None, out=None):
+    """(row_loss [B], dz [B, H] or None, dWo [I, H] or None, dbo [I] or None) of yr_cdae_catalogue_bce: torch's BCELoss
+    between act(z Wo^T + bo) and the 0/1 rows the per-user CSR (``tgt_ptr`` [K + 1], ``tgt_idx``, int64, item ids
+    ascending) gives the rows' ``users``, over ALL B I positions.  ``row_loss`` holds the rows' sums of terms (not
+    divided); the gradients carry the mean's 1 / (B I).  ``grads`` False is the loss-only call.  ``out``: the
+    (row_loss, dz, dWo, dbo) to write into instead of new tensors (a training step's own buffers)."""
+    lib = _lib.load()
+    f32, i64 = torch.float32, torch.int64
+    if z.dim() != 2 or Wo.dim() != 2 or z.shape[1] != Wo.shape[1]:
+        raise EngineError(f"cdae_catalogue_bce: z [B, H] and Wo [I, H] expected, got {tuple(z.shape)} / {tuple(Wo.shape)}")
+    (B, H), I = z.shape, Wo.shape[0]
+    if bo is None or bo.numel() != I:
+        raise EngineError("cdae_catalogue_bce: bo holds one entry per row of Wo")
+    if users.numel() != B:
+        raise EngineError("cdae_catalogue_bce: users holds one entry per row of z")
+    if tgt_ptr is None or tgt_idx is None or tgt_ptr.numel() < 1:
+        raise EngineError("cdae_catalogue_bce: the targets are a CSR (tgt_ptr [K + 1], tgt_idx)")
+    if int(act) not in (ACT_IDENTITY, ACT_SIGMOID):
+        raise EngineError("cdae_catalogue_bce: the output activation is the identity or the sigmoid")
+    K = tgt_ptr.numel() - 1
+    dev = z.device
+    if workspace is None:
+        n = cdae_catalogue_bce_workspace_floats(B, I, H)
+        workspace = torch.empty(n if grads else n // (1 + H), dtype=f32, device=dev)
+    if out is not None:
+        row_loss, dz, dWo, dbo = out
+        if row_loss.numel() != B or (grads and (dz.shape != (B, H) or dWo.shape != (I, H) or dbo.numel() != I)):
+            raise EngineError("cdae_catalogue_bce: out = (row_loss [B], dz [B, H], dWo [I, H], dbo [I])")
+        if not grads:
+            dz = dWo = dbo = None
+    else:
+        row_loss = torch.zeros(B, dtype=f32, device=dev)
+        dz = torch.empty((B, H), dtype=f32, device=dev) if grads else None
+        dWo = torch.empty((I, H), dtype=f32, device=dev) if grads else None
+        dbo = torch.empty(I, dtype=f32, device=dev) if grads else None
+    # an empty CSR has no storage to point at: its offsets array stands in (never dereferenced: every list is empty)
+    idx = _dev(tgt_idx, i64, "tgt_idx") if tgt_idx.numel() else _dev(tgt_ptr, i64, "tgt_ptr")
+    check(lib.yr_cdae_catalogue_bce(_dev(z, f32, "z"), _dev(Wo, f32, "Wo"), _dev(bo, f32, "bo"),
+                                    _dev(users, i64, "users"), _dev(tgt_ptr, i64, "tgt_ptr"), idx, B, I, K, H, int(act),
+                                    _dev(row_loss, f32, "row_loss") if B else None, _opt(dz, f32, "dz") if B else None,
+                                    _opt(dWo, f32, "dWo") if I else None, _opt(dbo, f32, "dbo") if I else None,
+                                    _dev(workspace, f32, "workspace") if workspace.numel() else None,
+                                    workspace.numel(), _opt(err_flag, torch.int32, "flag"), _stream()),
+          "yr_cdae_catalogue_bce")
+    return row_loss, dz, dWo, dbo
 
 
 def cdae_loss_finalize_batched(partial_loss, splits, loss_count, rows, batch_rows, means, arrive, loss_accum):

@@ -131,15 +131,18 @@ def build(cfg):
 
 
 CDAE_LIST_HIDDEN = (16, 32, 64, 128, 256, 512, 1024)
+CDAE_PLAIN_LIST_HIDDEN = (16, 32, 64, 128)      # negative_sampling=false: the catalogue sweep's widths
 
 
 def cdae_takes_list_batches(cfg, num_items):
     """CDAE batches as lists straight from the per-user CSR (no dense rows or masks)?  When the fused step and the
-    fused evaluation can take them: NS-BCE, Adam / AdamW, a hidden size the kernels are built for (the sweep grid's
-    powers of two), a top-n the fused evaluation has at that width (n <= 16 from 128 up)."""
+    fused evaluation can take them: Adam / AdamW, a hidden size the kernels are built for (NS-BCE: the sweep grid's
+    powers of two; plain BCE, ``negative_sampling=false``: the four widths of the catalogue sweep — wider models keep
+    dense batches there), a top-n the fused evaluation has at that width (n <= 16 from 128 up)."""
     from .engine import fused_eval_supports
-    return bool(cfg.get("list_batches", True)) and bool(cfg.negative_sampling) and bool(cfg.get("fused_step", True)) \
-        and cfg.optimizer.lower() in ("adam", "adamw") and cfg.hidden_size in CDAE_LIST_HIDDEN \
+    widths = CDAE_LIST_HIDDEN if cfg.negative_sampling else CDAE_PLAIN_LIST_HIDDEN
+    return bool(cfg.get("list_batches", True)) and bool(cfg.get("fused_step", True)) \
+        and cfg.optimizer.lower() in ("adam", "adamw") and cfg.hidden_size in widths \
         and bool(fused_eval_supports(cfg.top_n, cfg.hidden_size)) and num_items <= 163840
 
 
@@ -171,7 +174,8 @@ def train(cfg, args):
                 else cfg.batch_size
             mk = lambda mode, seed: CDAEBatchLoader(args.cdae_data, mode, rows(mode), cfg.neg_times,
                                                     shuffle=cfg.shuffle and mode != 'test', seed=seed, lists=as_lists,
-                                                    dropout=cfg.corruption_level)
+                                                    dropout=cfg.corruption_level,
+                                                    negative_sampling=bool(cfg.negative_sampling))
             train_dataloader, valid_dataloader, test_dataloader = mk('train', cfg.seed), mk('valid', cfg.seed + 1), mk('test', 0)
         else:
             test_dataloader = DataLoader(args.test_dataset, batch_size=cfg.batch_size)

@@ -109,10 +109,18 @@ class CDAETrainer(BaseTrainer):
         activation is monotone, so the top-k of the pre-activations is the reference's top-k of ``pred``; its
         multiply-mask (seen items -> 0, cdae_trainer.py:132) is below every sigmoid output, i.e. -FLT_MAX before
         the sigmoid (with the identity activation: the value 0 itself).
+        Under plain BCE (``negative_sampling`` off) the validation loss reads every position: the batches' lists
+        carry their target CSR instead of loss positions, and one loss-only catalogue sweep over the hidden rows of
+        all users (yr_cdae_catalogue_bce) gives the rows' loss sums, from which the per-batch means are formed.
         Returns the six metric sums of _metric_sums over the whole user set."""
         model, dev = self.model, self.device
-        if with_loss and not self.cfg.negative_sampling:
-            raise NotImplementedError("list batches carry the NS-BCE positions; plain BCE needs dense batches")
+        # plain BCE reads every catalogue position: no per-batch loss launch, one loss-only catalogue sweep over the
+        # hidden rows of all users once Z is filled (yr_cdae_catalogue_bce), at the widths it is built for
+        plain = with_loss and not self.cfg.negative_sampling
+        if plain and model.hidden_size not in engine.CDAE_CATALOGUE_HIDDEN:
+            raise NotImplementedError("plain BCE over list batches: hidden size 16 / 32 / 64 / 128; wider models need "
+                                      "dense batches")
+        order, bounds, targets = [], [], None
         Wh, bh, V, Wo, bo = (q.data for q in model._params())
         # the encoder gathers one column of W_h per input item: from a transposed copy ([I, H], made once per pass:
         # one 19.5 MB copy) that is one contiguous 4 H-byte row instead of H scattered cache lines — the encoder was
@@ -139,7 +147,12 @@ class CDAETrainer(BaseTrainer):
             Z.index_copy_(0, users, z)
             covered += users.numel()
             item_lists = data['item_lists']
-            if with_loss and grouped:
+            if plain:
+                rows = int(data.get('batch_rows', users.numel()))
+                order.append(users)
+                bounds.extend(min(rows, users.numel() - s) for s in range(0, users.numel(), rows))
+                targets = lists.targets
+            elif with_loss and grouped:
                 splits = engine.cdae_sampled_decode_splits(users.numel())
                 n = users.numel() * splits
                 if partials is None or partials.numel() < n:
@@ -160,6 +173,21 @@ class CDAETrainer(BaseTrainer):
                 engine.cdae_loss_finalize(partials, n, count, stats, self._loss_accum)
         if covered != model.num_users or item_lists is None:
             raise NotImplementedError("list batches must cover every user exactly once (CDAEBatchLoader does)")
+        if plain:
+            if targets is None:
+                raise NotImplementedError("plain BCE over list batches needs their target CSR "
+                                          "(CDAEBatchLoader(negative_sampling=False))")
+            # the reference's quantity (cdae_trainer.py:56-88): the sum over the batches, in loader order, of the mean
+            # over the batch's B_b I elements — from the rows' sums, batch by batch on the device
+            all_users = torch.arange(model.num_users, device=dev)
+            row_loss = engine.cdae_catalogue_bce(Z, Wo, bo, all_users, targets[0], targets[1], model._output_act,
+                                                 grads=False, err_flag=model._flag())[0]
+            sizes = torch.tensor(bounds, dtype=torch.int64, device=dev)
+            run = torch.cat([torch.zeros(1, dtype=torch.float64, device=dev),
+                             torch.cumsum(row_loss[torch.cat(order)].double(), 0)])      # a scan: one order
+            ends = torch.cumsum(sizes, 0)
+            sums = run[ends] - run[ends - sizes]
+            self._loss_accum += (sums / (sizes.double() * model.num_items)).sum()
         (sp, si), (ap, ai) = item_lists["seen"], item_lists["actual"]
         mask_value = engine.MASK_VALUE if model._output_act == engine.ACT_SIGMOID else 0.0
         # the previous lists of the same pass (validation / test) are the hint of this one (engine.mf_eval_topk)
