@@ -783,6 +783,42 @@ int yr_cdae_catalogue_bce(const float *z, const float *Wo, const float *bo, cons
                           int64_t workspace_floats, int32_t *err_flag, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * CDAE list-batch step, reproducible form: owner-pass gradients   (reference trainers/cdae_trainer.py:36-54, whose
+ *   runs repeat bit for bit under one seed; csrc/cdae_owned.hip)
+ * yr_cdae_owned_decode takes the operands of yr_cdae_sampled_decode with all three gradients, yr_cdae_owned_hidden_bwd
+ * those of yr_cdae_hidden_bwd_dwh_t, and they compute the same quantities with the same contracts (dz, dW_o, db_o
+ * without 1 / count; g as yr_cdae_sampled_decode states it; loss partials [B][splits] and the spread count exactly
+ * as that kernel gives them; count zero on entry) — but no float atomic touches memory: the entries of the batch's
+ * list are sorted by column (integer counts, a scan, an integer cursor), and the owner of a destination row sums its
+ * terms by ASCENDING batch row and stores each element once.  Two calls on the same operands agree bit for bit.
+ *   dz [B][H]           written whole (no zero-on-entry requirement): the splits' partials added in split order
+ *   dW_o [c], db_o [c]  stored for every column c with a loss position of the batch; other rows are not touched
+ *   db_h [H]            stored: the serial sum over the rows 0 .. B - 1
+ *   dV [u]              stored for every in-range user of the batch: its rows summed in ascending order (duplicates
+ *                       allowed; out-of-range users skipped); other rows are not touched
+ *   dW_h^T [item]       stored for every item with an input entry; other rows are not touched
+ *   marks, stats, loss_accum: as yr_cdae_hidden_bwd_dwh_t.
+ * A batch row must not hold one column twice in one list (the list builders never do).
+ * H: a power of two from 16 to 1,024 (YR_ERR_UNSUPPORTED otherwise, and when the B x 32 x
+ * yr_cdae_sparse_part_columns(I) list slots of a batch do not fit 31 bits).
+ * workspace: yr_cdae_owned_workspace_bytes(B, I, H) bytes (a negative YR_ERR_* for refused sizes), 16-byte aligned,
+ * any contents: both calls share one (they run one after the other).  Checked before any launch: negative sizes,
+ * I <= 0, H <= 0, an act other than 0 / 1: YR_ERR_BADARG; the width: YR_ERR_UNSUPPORTED; then B == 0: 0 (nothing is
+ * written); then null pointers, z / W_o / workspace off a 16-byte boundary, a workspace too small: YR_ERR_BADARG.
+ * ------------------------------------------------------------------------- */
+int64_t yr_cdae_owned_workspace_bytes(int64_t B, int64_t I, int H);
+int yr_cdae_owned_decode(const int32_t *loss_cols, const float *loss_targets, const int32_t *loss_count,
+                         const float *z, const float *Wo, const float *bo, int64_t B, int64_t I, int H, int act,
+                         float *dz, float *dWo, float *dbo, float *partial_loss, int32_t *count, void *workspace,
+                         int64_t workspace_bytes, void *stream);
+int yr_cdae_owned_hidden_bwd(const int32_t *cols, const float *vals, const int32_t *count, const float *dz,
+                             const float *z, int act, int scale_dz, const int32_t *pos_count,
+                             const int64_t *user, int64_t B, int64_t I, int H, int64_t num_users, float *dV,
+                             uint8_t *touched_users, float *dbh, float *dWhT, uint8_t *touched_items,
+                             const float *partial_loss, int64_t n_partials, float *stats, double *loss_accum,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------
  * Device-side BPR triplet stream  (reference train.py:76-77: DataLoader(MFDataset, shuffle=True);
  *   data/datasets/mf_dataset.py:18-32: __getitem__ + _negative_sampling)
  * Stream positions [first, first + count) of epoch `epoch`: position t reads row P(t) of

@@ -93,6 +93,13 @@ BUDGETS = [
     (r"void yr::cdae_cbce_kernel<128, (true|false)>", 512, 17 * 1024,
      "as above at H = 128: 64 + 64 row registers, one wave per SIMD; 16.1 KB of LDS for the wave-order sum; no scratch"),
     (r"yr::cdae_cbce_reduce_kernel", 64, 0, "streaming sums of the chunks' partials in a fixed order"),
+    # CDAE list-batch step, reproducible form (csrc/cdae_owned.hip; figures in profiles/cdae_owned_resources.txt)
+    (r"void yr::cdae_owned_decode_kernel<(32|64), (4|8|16), (true|false)>", 128, 34 * 1024,
+     "the default decoder's geometry and budget: four waves per SIMD, the staged list + the groups' dz rows in LDS"),
+    (r"void yr::cdae_owned_gather_kernel<(1|2|4|8|16), (true|false)>", 96, 0,
+     "a column owner keeps H / lanes accumulators and one row of the operand: five waves per SIMD at 16 floats per lane"),
+    (r"yr::cdae_owned_(count|scan|sum_splits|hidden_rows|hidden_sums)_kernel", 64, 2 * 1024,
+     "integer counting sort and streaming row passes: eight waves per SIMD"),
 ]
 # Scratch (spilled registers) per lane.  The forms the benchmark and the trainers run by default — width 64, summation
 # order free — must have none; the deterministic-order forms and some forms of the other widths are held at 64 VGPRs by

@@ -112,6 +112,10 @@ SIGNATURES = {
                                  _i64, _p, _p, _p],
     "yr_cdae_catalogue_bce_workspace_floats": [_i64, _i64, _int],
     "yr_cdae_catalogue_bce": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _p, _p, _p, _p, _i64, _p, _p],
+    "yr_cdae_owned_workspace_bytes": [_i64, _i64, _int],
+    "yr_cdae_owned_decode": [_p, _p, _p, _p, _p, _p, _i64, _i64, _int, _int, _p, _p, _p, _p, _p, _p, _i64, _p],
+    "yr_cdae_owned_hidden_bwd": [_p, _p, _p, _p, _p, _int, _int, _p, _p, _i64, _i64, _int, _i64, _p, _p, _p, _p, _p, _p,
+                                 _i64, _p, _p, _p, _i64, _p],
     "yr_triplet_sample": [_p, _p, _i64, _p, _p, _i64, _i64, C.c_uint64, C.c_uint64, _int, _i64, _i64,
                           _p, _p, _p, _p, _p],
     "yr_dcn_assemble": [_p, _p, _p, _p, _p, _p, _int, _int, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _int, _p, _i64,
@@ -147,7 +151,7 @@ RESTYPES.update({name: _i64 for name in (
     "yr_cdae_decode_loss_partials", "yr_mf_eval_topk_workspace_bytes", "yr_mf_eval_topk_planes_bytes",
     "yr_ngcf_step_workspace_bytes", "yr_ngcf_eval_topk_workspace_bytes", "yr_s3rec_train_workspace_floats",
     "yr_s3rec_catalogue_bce_workspace_floats", "yr_s3rec_catalogue_rank_workspace_bytes",
-    "yr_cdae_catalogue_bce_workspace_floats")})
+    "yr_cdae_catalogue_bce_workspace_floats", "yr_cdae_owned_workspace_bytes")})
 
 _lib = None
 

@@ -37,6 +37,13 @@ that is the dense decoder above.  On list batches (``step_lists``, hidden size 1
 call, yr_cdae_catalogue_bce (csrc/cdae_catalogue.hip): the targets are the per-user item lists, the loss is taken in
 the epilogue of a matrix sweep and the pre-activations are computed again for dW_o / db_o — no [B, I] array, no float
 atomics, dz / dW_o / db_o final (1 / (B I) applied in the kernel) and each written whole.
+
+``deterministic=True`` (list batches only): the sampled decoder and the fused hidden backward add dW_o, db_o, dz across
+a row's splits, db_h, dV and dW_h^T with global float atomics, i.e. in arrival order.  In the mode yr_cdae_owned_decode
+and yr_cdae_owned_hidden_bwd (csrc/cdae_owned.hip) stand in their places: the batch's list entries are sorted by column
+with integer counts and cursors, and every gradient row is summed by its one owner over the batch rows in ascending
+order and stored once.  The encoder, the loss partials, the catalogue sweep and the Adam launch are ordered already, so
+two runs from one state end in the same bits (the reference's runs repeat under its seed).
 """
 import torch
 
@@ -44,10 +51,16 @@ from . import engine, optim
 
 
 WIDE_HIDDEN = (512, 1024)      # hidden sizes above 256 with the sampled decoder, row marks and the transposed W_h
+OWNED_HIDDEN = (16, 32, 64, 128, 256, 512, 1024)   # the widths csrc/cdae_owned.hip is built for
+DETERMINISTIC_NEEDS = ("CDAE deterministic=True: list batches (fast_loader=true, CDAEStep.step_lists) through the fused "
+                       "Adam / AdamW step with the transposed W_h, hidden size 16 / 32 / 64 / 128 / 256 / 512 / 1024 under "
+                       "NS-BCE or 16 / 32 / 64 / 128 under plain BCE; dense batches, SGD, fused_step=false and other "
+                       "widths add their gradients in arrival order and are refused rather than run unordered")
 
 
 class CDAEStep:
-    def __init__(self, model, optimizer, negative_sampling=True, decoder="auto", transposed_wh=False, row_marks=True):
+    def __init__(self, model, optimizer, negative_sampling=True, decoder="auto", transposed_wh=False, row_marks=True,
+                 deterministic=False):
         """``decoder``: "sampled" — forward, loss and the three decoder gradients on the loss positions only
         (NS-BCE reads nothing else; needs a negative mask), "dense" — the full-catalogue products on the matrix
         cores, "auto" — sampled when the loss is NS-BCE and the hidden size allows it (a multiple of 4 whose quarter is
@@ -62,7 +75,13 @@ class CDAEStep:
         ``row_marks``: False keeps the step off row marks at any width — every Adam launch then reads and clears all of
         dW_h and dV, and there is no transposed working copy (what every hidden size without marks runs, e.g. 320;
         scripts/bench_cdae_wide.py times the widths 512 / 1,024 that way for comparison).  With the default, marks hold
-        wherever the width allows them, for the dense decoder too."""
+        wherever the width allows them, for the dense decoder too.
+        ``deterministic``: every gradient of a ``step_lists`` step is summed by the owner of its destination over the
+        batch rows in ascending order (csrc/cdae_owned.hip) — no float atomics, so two runs from one state end in the
+        same bits.  NS-BCE: yr_cdae_owned_decode and yr_cdae_owned_hidden_bwd stand where the sampled decoder and the
+        fused hidden backward run; plain BCE: the catalogue sweep is ordered already, only the hidden backward changes.
+        Needs what DETERMINISTIC_NEEDS lists (NotImplementedError otherwise — there is no unordered fall-back), and
+        ``step`` on dense batches raises."""
         from . import optim
         if not isinstance(optimizer, optim.Adam):
             raise NotImplementedError("CDAEStep: optimizer adam or adamw")
@@ -86,6 +105,10 @@ class CDAEStep:
         self._cat = None                               # (B, row_loss, spread count B I, workspace) of step_lists
         self.transposed_wh = bool(transposed_wh) and self.row_marks
         self._wht = None                               # (WhT, mT, vT, dWhT, item marks) while acquired
+        self.deterministic = bool(deterministic)
+        if self.deterministic and not (self.row_marks and self.transposed_wh and H in OWNED_HIDDEN
+                                       and (self.decoder == "sampled" or self.catalogue)):
+            raise NotImplementedError(DETERMINISTIC_NEEDS)
         dev = self.params[0].device
         Wh, bh, V, Wo, bo = (p.data for p in self.params)
         f32 = torch.float32
@@ -154,6 +177,8 @@ class CDAEStep:
                 self.G = None                             # [B, I]: made by the first dense batch (step_lists needs none)
                 self.n_partials = engine.cdae_decode_loss_partials(B, I)
             self.partials = torch.empty(self.n_partials, dtype=f32, device=dev)
+            self._owned = (torch.empty(engine.cdae_owned_workspace_bytes(B, I, H), dtype=torch.uint8, device=dev)
+                           if self.deterministic else None)
             self._batch = B
 
     @torch.no_grad()
@@ -161,6 +186,8 @@ class CDAEStep:
         """One training step on the batch.  ``x``: the uncorrupted [B, I] input (the loss target);
         ``negative_mask``: [B, I] or None (plain BCE over every position).  The encoder input is
         dropout_p(x) with the Philox mask of ``seed`` — or ``x_in`` when given (an already corrupted input)."""
+        if self.deterministic:
+            raise NotImplementedError(DETERMINISTIC_NEEDS)
         model = self.model
         Wh, bh, V, Wo, bo = (q.data for q in self.params)
         B = x.shape[0]
@@ -236,6 +263,10 @@ class CDAEStep:
             engine.cdae_catalogue_bce(self.z, Wo, bo, user_id, targets[0], targets[1], model._output_act,
                                       workspace=workspace, err_flag=self.flag,
                                       out=(partials, self.dz, self.dWo, self.dbo))
+        elif sampled and self.deterministic:
+            self._blob.zero_()                           # the position counter (dz is written whole)
+            engine.cdae_owned_decode(loss_lists, self.z, Wo, bo, model._output_act, self.dz, self.dWo, self.dbo,
+                                     self.partials, self.count, self._owned)
         elif sampled:
             self._blob.zero_()
             engine.cdae_sampled_decode(loss_lists, self.z, Wo, bo, model._output_act, self.dz, self.dWo,
@@ -250,7 +281,12 @@ class CDAEStep:
             engine.gemm_f32(self.G, self.z, transA=True, out=self.dWo, alpha_count=self.count, rowsum=self.dbo)
             engine.gemm_f32(self.G, Wo, out=self.dz, accumulate=True, split_k=max(1, min(256, Wo.shape[0] // 256)),
                             alpha_count=self.count)
-        if wt is not None and self.hidden_size <= 1024:
+        if self.deterministic:
+            # as below, every sum by the owner of its destination in ascending row order (db_h, dV and dW_h^T stored)
+            engine.cdae_owned_hidden_bwd(rows, self.dz, self.z, model._hidden_act, user_id, count, self.dV,
+                                         self.touched_users, self.dbh, wt[3], wt[4], partials, n_partials,
+                                         self.stats, self.loss_accum, self._owned, scale_dz=sampled)
+        elif wt is not None and self.hidden_size <= 1024:
             # hidden layer's backward, db_h, dV, dW_h^T and the step's loss in one launch (db_h accumulates: the
             # Adam launch clears it)
             engine.cdae_hidden_bwd_dwh_t(rows, self.dz, self.z, model._hidden_act, user_id, count, self.dV,

@@ -837,6 +837,80 @@ def cdae_hidden_bwd_dwh_t(rows: "SparseRows", dz, z, act, user, count, dV, touch
                                        _stream()), "yr_cdae_hidden_bwd_dwh_t")
 
 
+# ---- the reproducible form of the list-batch step (csrc/cdae_owned.hip: owner-pass gradients, no float atomics) ----
+CDAE_OWNED_HIDDEN = (16, 32, 64, 128, 256, 512, 1024)
+
+
+def cdae_owned_workspace_bytes(B, I, H):
+    """Bytes of the workspace yr_cdae_owned_decode and yr_cdae_owned_hidden_bwd share (yr_cdae_owned_workspace_bytes)."""
+    n = _lib.load().yr_cdae_owned_workspace_bytes(int(B), int(I), int(H))
+    if n < 0:
+        check(int(n), "yr_cdae_owned_workspace_bytes")
+    return int(n)
+
+
+def _owned_workspace(workspace, B, I, H, what):
+    if workspace is None or not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise EngineError(f"{what}: workspace must be a contiguous uint8 device tensor")
+    if workspace.numel() < cdae_owned_workspace_bytes(B, I, H):
+        raise EngineError(f"{what}: workspace smaller than cdae_owned_workspace_bytes({B}, {I}, {H})")
+    return workspace.data_ptr(), workspace.numel()
+
+
+def cdae_owned_decode(loss_lists, z, Wo, bo, act, dz, dWo, dbo, partial_loss, count, workspace):
+    """cdae_sampled_decode with all three gradients, every sum by the owner of its destination in ascending row order
+    (yr_cdae_owned_decode): dz written whole, dWo / dbo rows of the batch's loss columns stored, nothing else touched;
+    ``count`` zero on entry.  Two calls on the same operands give the same bits."""
+    lib = _lib.load()
+    f32 = torch.float32
+    lc, lv, ln = loss_lists
+    if z.dim() != 2 or Wo.dim() != 2 or z.shape[1] != Wo.shape[1]:
+        raise EngineError(f"cdae_owned_decode: z [B, H] and Wo [I, H] expected, got {tuple(z.shape)} / {tuple(Wo.shape)}")
+    (B, H), I = z.shape, Wo.shape[0]
+    if dz is None or dWo is None or dbo is None or dz.shape != (B, H) or dWo.shape != (I, H) or dbo.numel() != I:
+        raise EngineError("cdae_owned_decode: dz [B, H], dWo [I, H] and dbo [I] are all required")
+    if bo is not None and bo.numel() != I:
+        raise EngineError("cdae_owned_decode: bo holds one entry per row of Wo")
+    if partial_loss.numel() < B * cdae_sampled_decode_splits(B) or count.numel() != COUNT_WORDS:
+        raise EngineError("bad buffers for cdae_owned_decode")
+    n = B * SPARSE_PARTS * sparse_part_columns(I) if I else 0
+    if lc.numel() < n or lv.numel() < n or ln.numel() < B * SPARSE_PARTS:
+        raise EngineError("cdae_owned_decode: loss list buffers too small")
+    ws, ws_bytes = _owned_workspace(workspace, B, I, H, "cdae_owned_decode")
+    check(lib.yr_cdae_owned_decode(_dev(lc, torch.int32, "loss_cols"), _dev(lv, f32, "loss_targets"),
+                                   _dev(ln, torch.int32, "loss_count"), _dev(z, f32, "z"), _dev(Wo, f32, "Wo"),
+                                   _opt(bo, f32, "bo"), B, I, H, int(act), _dev(dz, f32, "dz"), _dev(dWo, f32, "dWo"),
+                                   _dev(dbo, f32, "dbo"), _dev(partial_loss, f32, "partial_loss"),
+                                   _dev(count, torch.int32, "count"), ws, ws_bytes, _stream()), "yr_cdae_owned_decode")
+
+
+def cdae_owned_hidden_bwd(rows: "SparseRows", dz, z, act, user, count, dV, touched_users, dbh, dWhT, touched_items,
+                          partial_loss, n_partials, stats, loss_accum, workspace, scale_dz=False):
+    """cdae_hidden_bwd_dwh_t with every sum by the owner of its destination in ascending row order
+    (yr_cdae_owned_hidden_bwd): ``dbh``, the ``dV`` rows of the batch's users and the ``dWhT`` rows of its input items
+    are stored, not added to."""
+    lib = _lib.load()
+    f32 = torch.float32
+    if dz.dim() != 2 or z.shape != dz.shape or dV.dim() != 2 or dV.shape[1] != dz.shape[1]:
+        raise EngineError("cdae_owned_hidden_bwd: dz and z [B, H], dV [users, H] expected")
+    B, H = dz.shape
+    if rows.B != B or user.numel() != B or dbh.numel() != H or dWhT.shape != (rows.I, H) or touched_items.numel() != rows.I:
+        raise EngineError("cdae_owned_hidden_bwd: rows, user [B], dbh [H], dWhT [I, H] and touched_items [I] must agree")
+    if count.numel() != COUNT_WORDS:
+        raise EngineError(f"count: a spread count of {COUNT_WORDS} int32 words")
+    ws, ws_bytes = _owned_workspace(workspace, B, rows.I, H, "cdae_owned_hidden_bwd")
+    check(lib.yr_cdae_owned_hidden_bwd(_dev(rows.cols, torch.int32, "cols"), _dev(rows.vals, f32, "vals"),
+                                       _dev(rows.count, torch.int32, "count"),
+                                       _dev(dz, f32, "dz"), _dev(z, f32, "z"), int(act), 1 if scale_dz else 0,
+                                       _dev(count, torch.int32, "count"), _dev(user, torch.int64, "user"), B,
+                                       rows.I, H, dV.shape[0], _dev(dV, f32, "dV"),
+                                       _opt(touched_users, torch.uint8, "touched_users"), _dev(dbh, f32, "dbh"),
+                                       _dev(dWhT, f32, "dWhT"), _dev(touched_items, torch.uint8, "touched_items"),
+                                       _opt(partial_loss, f32, "partial_loss"), int(n_partials),
+                                       _opt(stats, f32, "stats"), _opt(loss_accum, torch.float64, "loss_accum"),
+                                       ws, ws_bytes, _stream()), "yr_cdae_owned_hidden_bwd")
+
+
 _dwh_scratch = {}
 
 

@@ -165,6 +165,10 @@ def train(cfg, args):
         valid_dataloader = DataLoader(args.valid_dataset, batch_size=cfg.batch_size, shuffle=cfg.shuffle)
     if cfg.model_name == 'CDAE':
         from .trainers.cdae_trainer import CDAETrainer
+        if cfg.get("deterministic", False) and not (cfg.get("fast_loader") and
+                                                    cdae_takes_list_batches(cfg, args.cdae_data.num_items)):
+            from .cdae_step import DETERMINISTIC_NEEDS       # refused before training starts, never run unordered
+            raise NotImplementedError(DETERMINISTIC_NEEDS)
         if cfg.get("fast_loader"):
             from .data.cdae_batches import CDAEBatchLoader
             as_lists = cdae_takes_list_batches(cfg, args.cdae_data.num_items)

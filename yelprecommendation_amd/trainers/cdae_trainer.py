@@ -16,7 +16,7 @@ import torch
 from .. import engine
 from ..loss import BCELoss, NSBCELoss
 from ..metric import ranking_metrics
-from ..cdae_step import CDAEStep
+from ..cdae_step import CDAEStep, DETERMINISTIC_NEEDS
 from ..models.cdae import CDAE
 from ..utils import log_metric, logger
 from .base_trainer import BaseTrainer
@@ -52,13 +52,16 @@ class CDAETrainer(BaseTrainer):
         if self._step is None or not self._step.bound_to(self.model, self.optimizer):
             self._step = CDAEStep(self.model, self.optimizer, self.cfg.negative_sampling,
                                   decoder=self.cfg.get("train_decoder", "auto"),
-                                  transposed_wh=self.cfg.get("transposed_wh", True))
+                                  transposed_wh=self.cfg.get("transposed_wh", True),
+                                  deterministic=bool(self.cfg.get("deterministic", False)))
         return self._step
 
     def train(self, train_dataloader) -> float:
         # reference cdae_trainer.py:36-54
         self.model.train()
         step = self._fused_step()
+        if self.cfg.get("deterministic", False) and (step is None or not getattr(train_dataloader, "lists", False)):
+            raise NotImplementedError(DETERMINISTIC_NEEDS)     # the autograd route and dense batches add in arrival order
         if step is not None:
             step.loss_accum.zero_()
             try:
