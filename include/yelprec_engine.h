@@ -374,6 +374,56 @@ int yr_ngcf_bpr_step(const int32_t *rowptr, const int32_t *col, const float *val
                      int32_t *err_flag, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * NGCF, reproducible step (csrc/ngcf_owned.hip).  The reference's runs repeat bit for bit under one seed
+ * (trainers/ngcf_trainer.py:104-116 after utils.py's seeding); yr_ngcf_bpr_step does not: it sums the layer
+ * gradients and dW with float atomics and lists a batch's row sets in arrival order.  The entry points below issue no
+ * float atomic: every gradient element is summed by the one owner of its destination in a fixed order and written
+ * with a plain store, so two calls on the same inputs give the same bits.
+ *
+ * yr_ngcf_owned_score_bwd: yr_ngcf_score_bwd (the autograd of models/ngcf.py:44-58, loss.backward() at
+ *   trainers/ngcf_trainer.py:112) with dlayers[k][row] = its content on entry + the row's per-triplet contributions
+ *   in ascending triplet index, one f32 add each, for a row of any number of contributions: on a user row
+ *   fmaf(gneg, E_k[U + neg], gpos * E_k[U + pos]) (gpos * E_k[U + pos] without negatives), on an item row
+ *   gpos * E_k[user] as positive, then gneg * E_k[user] as negative.  Rows no triplet touches are not written.
+ *   Out-of-range ids: flag raised, triplet skipped.  workspace: yr_ngcf_owned_score_workspace_bytes(n, B) bytes
+ *   (n = num_users + num_items; a negative YR_ERR_* for refused sizes: 4 B + 2 must fit an int32), 16-byte aligned,
+ *   contents irrelevant on entry.  Layer and gradient buffers 16-byte aligned.
+ * yr_ngcf_owned_dense_bwd_weight: yr_ngcf_dense_bwd_weight (rows = count = NULL) or yr_ngcf_dense_bwd_weight_rows —
+ *   the dW part of loss.backward() through models/ngcf.py:69-70 — with every workgroup's 2 D^2 partial sums stored to
+ *   its own slot of the workspace and dW1 | dW2 += the slots of the workgroups that had rows, in ascending workgroup
+ *   order (at most 256 workgroups).  workspace: yr_ngcf_owned_dw_workspace_bytes(rows, D) bytes serve every call
+ *   over at most `rows` rows (n, or max_rows of the row-list form); 16-byte aligned like dW1 / dW2; contents
+ *   irrelevant on entry, unwritten slots are never read.
+ * yr_ngcf_frontier_order: rows[0 .. *count) = the members of `flags` (int32[n], 16-byte aligned) in ASCENDING order,
+ *   *count = their number: after yr_ngcf_frontier_mark / _expand, whose lists are in arrival order
+ *   (models/ngcf.py:37-39: the rows bpr_forward reads).
+ * yr_ngcf_bpr_step_ordered: yr_ngcf_bpr_step (same arguments, same reference lines) built from those three: the
+ *   row sets ordered, the score gradient and dW by their owner passes, the backward product of a restricted layer
+ *   always the pull form (no yr_spmm_csr_push_rows).  workspace: yr_ngcf_step_ordered_workspace_bytes(n, D, K, B)
+ *   bytes, 256-byte aligned, contents irrelevant on entry.
+ * ------------------------------------------------------------------------- */
+int64_t yr_ngcf_owned_score_workspace_bytes(int64_t n, int64_t B);
+int yr_ngcf_owned_score_bwd(const float *const *layers, float *const *dlayers, int n_layers, const int64_t *user,
+                            const int64_t *pos, const int64_t *neg, const float *gpos, const float *gneg,
+                            int64_t B, int D, int64_t num_users, int64_t num_items,
+                            void *workspace, int64_t workspace_bytes, int32_t *err_flag, void *stream);
+int64_t yr_ngcf_owned_dw_workspace_bytes(int64_t rows, int D);
+int yr_ngcf_owned_dense_bwd_weight(const float *dEout, const float *Eout, const float *E, const float *Z,
+                                   int64_t n, int D, float *dW1, float *dW2,
+                                   const int32_t *rows, const int32_t *count, int64_t max_rows,
+                                   void *workspace, int64_t workspace_bytes, void *stream);
+int yr_ngcf_frontier_order(const int32_t *flags, int64_t n, int32_t *rows, int32_t *count, void *stream);
+int64_t yr_ngcf_step_ordered_workspace_bytes(int64_t n, int D, int K, int64_t B);
+int yr_ngcf_bpr_step_ordered(const int32_t *rowptr, const int32_t *col, const float *val, int64_t n, int64_t nnz,
+                             const int32_t *heavy_rows, int64_t n_heavy, int heavy_threshold, int64_t num_users,
+                             float *const *params, float *const *exp_avg, float *const *exp_avg_sq, int K, int D,
+                             const int64_t *user, const int64_t *pos, const int64_t *neg, int64_t B,
+                             double lr, double step_size, double bc2_sqrt, double beta1, double beta2, double eps,
+                             double weight_decay, int mode, double subset_fraction,
+                             void *workspace, int64_t workspace_bytes, float *loss_out, double *loss_accum,
+                             int32_t *err_flag, void *stream);
+
+/* ---------------------------------------------------------------------------
  * CDAE                        (reference models/cdae.py:46-52, loss.py:12-16 and their autograd)
  *
  * yr_gemm_f32: C[M,N] (+)= op(A)[M,K] . op(B)[K,N] on v_mfma_f32_32x32x2_f32 (exact f32), row-major,

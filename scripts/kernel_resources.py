@@ -98,8 +98,20 @@ BUDGETS = [
      "the default decoder's geometry and budget: four waves per SIMD, the staged list + the groups' dz rows in LDS"),
     (r"void yr::cdae_owned_gather_kernel<(1|2|4|8|16), (true|false)>", 96, 0,
      "a column owner keeps H / lanes accumulators and one row of the operand: five waves per SIMD at 16 floats per lane"),
-    (r"yr::cdae_owned_(count|scan|sum_splits|hidden_rows|hidden_sums)_kernel", 64, 2 * 1024,
+    (r"yr::cdae_owned_(count|sum_splits|hidden_rows|hidden_sums)_kernel", 64, 2 * 1024,
      "integer counting sort and streaming row passes: eight waves per SIMD"),
+    (r"void yr::owned_scan_kernel<(true|false)>", 64, 1024,
+     "the tiled integer scan of the owner passes (owned_scan.h; CDAE and NGCF): eight waves per SIMD"),
+    # NGCF fused step, reproducible form (csrc/ngcf_owned.hip; figures in profiles/ngcf_owned_resources.txt)
+    (r"void yr::ngcf_owned_score_bwd_kernel<(16|32|64|128), (true|false)>", 64, 0,
+     "a lane group per row, one accumulator and four contributions' rows ahead: eight waves per SIMD to hide the "
+     "three dependent loads per contribution"),
+    (r"yr::ngcf_owned_(count|fill|rank|dw_reduce)_kernel", 64, 0,
+     "integer counting sort, the rank pass and the slot sum (eight slots' loads in flight): eight waves per SIMD"),
+    (r"void yr::ngcf_owned_dw_slots_kernel<(16|32|64), (true|false)>", 176, 48 * 1024,
+     "ngcf_dense_bwd_weight_kernel with a store epilogue: the same body, so the same registers and 48 KB of LDS"),
+    (r"void yr::ngcf_owned_dw_slots_kernel<128, (true|false)>", 512, 48 * 1024,
+     "as above at D = 128: 8 output tiles per wave (128 accumulators), one wave per SIMD as the default kernel"),
 ]
 # Scratch (spilled registers) per lane.  The forms the benchmark and the trainers run by default — width 64, summation
 # order free — must have none; the deterministic-order forms and some forms of the other widths are held at 64 VGPRs by

@@ -54,6 +54,14 @@ SIGNATURES = {
     "yr_ngcf_step_workspace_bytes": [_i64, _int, _int, _i64],
     "yr_ngcf_bpr_step": [_p, _p, _p, _i64, _i64, _p, _i64, _int, _i64, _p, _p, _p, _int, _int, _p, _p, _p, _i64,
                          _d, _d, _d, _d, _d, _d, _d, _int, _d, _p, _i64, _p, _p, _p, _p],
+    "yr_ngcf_owned_score_workspace_bytes": [_i64, _i64],
+    "yr_ngcf_owned_score_bwd": [_p, _p, _int, _p, _p, _p, _p, _p, _i64, _int, _i64, _i64, _p, _i64, _p, _p],
+    "yr_ngcf_owned_dw_workspace_bytes": [_i64, _int],
+    "yr_ngcf_owned_dense_bwd_weight": [_p, _p, _p, _p, _i64, _int, _p, _p, _p, _p, _i64, _p, _i64, _p],
+    "yr_ngcf_frontier_order": [_p, _i64, _p, _p, _p],
+    "yr_ngcf_step_ordered_workspace_bytes": [_i64, _int, _int, _i64],
+    "yr_ngcf_bpr_step_ordered": [_p, _p, _p, _i64, _i64, _p, _i64, _int, _i64, _p, _p, _p, _int, _int, _p, _p, _p,
+                                 _i64, _d, _d, _d, _d, _d, _d, _d, _int, _d, _p, _i64, _p, _p, _p, _p],
     "yr_gemm_f32": [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _int, _int, _int, _p],
     "yr_gemm_f32_ex": [_int, _int, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _int, _int, _int, _p, _p, _p],
     "yr_cdae_decode_loss_partials": [_i64, _i64],
@@ -151,7 +159,9 @@ RESTYPES.update({name: _i64 for name in (
     "yr_cdae_decode_loss_partials", "yr_mf_eval_topk_workspace_bytes", "yr_mf_eval_topk_planes_bytes",
     "yr_ngcf_step_workspace_bytes", "yr_ngcf_eval_topk_workspace_bytes", "yr_s3rec_train_workspace_floats",
     "yr_s3rec_catalogue_bce_workspace_floats", "yr_s3rec_catalogue_rank_workspace_bytes",
-    "yr_cdae_catalogue_bce_workspace_floats", "yr_cdae_owned_workspace_bytes")})
+    "yr_cdae_catalogue_bce_workspace_floats", "yr_cdae_owned_workspace_bytes",
+    "yr_ngcf_owned_score_workspace_bytes", "yr_ngcf_owned_dw_workspace_bytes",
+    "yr_ngcf_step_ordered_workspace_bytes")})
 
 _lib = None
 

@@ -26,6 +26,7 @@
 #include <climits>
 #include "common.h"
 #include "cdae_rows.h"
+#include "owned_scan.h"
 
 namespace yr {
 
@@ -46,52 +47,7 @@ __global__ __launch_bounds__(kBlock) void cdae_owned_count_kernel(const int32_t*
   for_row_entries(cols, count, cpp, blockIdx.x, [&](int32_t c, int64_t) { atomicAdd(cnt + c, 1); });
 }
 
-// start[c] = entries of the columns before c, start[I] = all of them.  A workgroup per tile of kScanTile columns: it
-// sums the counts of every column before its tile itself (coalesced, at most 4 I bytes out of L2 — one launch, no
-// hand-off between workgroups; a single workgroup walking all of I = 38,048 took 85 us) and scans its own tile.
-constexpr int kScanPerThread = 4;
-constexpr int kScanTile = kScanPerThread * kBlock;
-static_assert(kScanPerThread == 4, "the counts before a tile are read as int4");
-
-__global__ __launch_bounds__(kBlock) void cdae_owned_scan_kernel(const int32_t* __restrict__ cnt, int64_t I,
-                                                                 int32_t* __restrict__ start) {
-  __shared__ int s_before[kWavesPerBlock];
-  __shared__ int s_incl[kWavesPerBlock];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const int64_t lo = (int64_t)blockIdx.x * kScanTile;
-  int before = 0;                                   // lo is a multiple of the tile; cnt is 16-byte aligned
-#pragma unroll 4
-  for (int64_t i = (int64_t)threadIdx.x * kScanPerThread; i < lo; i += kScanTile) {
-    const int4 t = *reinterpret_cast<const int4*>(cnt + i);
-    before += (t.x + t.y) + (t.z + t.w);
-  }
-  const int64_t at = lo + (int64_t)threadIdx.x * kScanPerThread;
-  int v[kScanPerThread], mine = 0;
-#pragma unroll
-  for (int k = 0; k < kScanPerThread; ++k) {
-    v[k] = at + k < I ? cnt[at + k] : 0;
-    mine += v[k];
-  }
-  int incl = mine;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int t = __shfl_up(incl, d, kWave);
-    if (lane >= d) incl += t;
-  }
-#pragma unroll
-  for (int d = kWave / 2; d >= 1; d >>= 1) before += __shfl_xor(before, d, kWave);
-  if (lane == kWave - 1) s_incl[wave] = incl;
-  if (lane == 0) s_before[wave] = before;
-  __syncthreads();
-  int run = incl - mine;
-  for (int w = 0; w < kWavesPerBlock; ++w) run += s_before[w] + (w < wave ? s_incl[w] : 0);
-#pragma unroll
-  for (int k = 0; k < kScanPerThread; ++k) {
-    if (at + k < I) start[at + k] = run;
-    run += v[k];
-  }
-  if (at < I && at + kScanPerThread >= I) start[I] = run;       // the thread that holds the last column
-}
+// (start[c] = entries of the columns before c, start[I] = all of them: owned_scan_kernel<false>, owned_scan.h)
 
 // The decoder on the loss positions, a workgroup per (row, split): geometry, position order and loss sums of
 // cdae_sampled_decode_kernel<LPP, EPL, EXACT, false>, so the loss partials and the count are the default kernel's.
@@ -397,8 +353,8 @@ int owned_sort_prologue(const int32_t* cols, const int32_t* count, int64_t B, in
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(cdae_owned_count_kernel, dim3((unsigned)B), dim3(kBlock), 0, s, cols, count,
                      yr_cdae_sparse_part_columns(I), p.cnt);
-  hipLaunchKernelGGL(cdae_owned_scan_kernel, dim3((unsigned)((I + kScanTile - 1) / kScanTile)), dim3(kBlock), 0, s,
-                     p.cnt, I, p.start);
+  hipLaunchKernelGGL(owned_scan_kernel<false>, dim3((unsigned)owned_scan_grid(I)), dim3(kBlock), 0, s, p.cnt, I,
+                     p.start, (int32_t*)nullptr);
   return launch_status();
 }
 

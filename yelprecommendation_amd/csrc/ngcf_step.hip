@@ -81,8 +81,11 @@ static inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 struct StepLayout {
   // zeroed by the step's first launch: [flags of the K row sets | their counts | dW] — one contiguous range
-  int64_t layers, Z, dlayers, dZ, zero_begin, flags, counts, dW, zero_end, rows, scores, WT, partials, total;
-  StepLayout(int64_t n, int D, int K, int64_t B) {
+  // ordered (yr_ngcf_bpr_step_ordered) appends the scratch of the owner passes (csrc/ngcf_owned.hip): the counting sort
+  // of the score backward and the workgroup slots of the weight gradient; the other offsets do not move
+  int64_t layers, Z, dlayers, dZ, zero_begin, flags, counts, dW, zero_end, rows, scores, WT, partials, owned_score,
+      owned_score_bytes, dw_slots, dw_slots_bytes, total;
+  StepLayout(int64_t n, int D, int K, int64_t B, bool ordered = false) {
     const int64_t nd = align256(n * D * 4);
     int64_t at = 0;
     layers = at;   at += (int64_t)K * nd;
@@ -98,6 +101,10 @@ struct StepLayout {
     scores = at;   at += 4 * align256(B * 4);
     WT = at;       at += align256((int64_t)2 * K * D * D * 4);
     partials = at; at += align256(YR_LOSS_PARTIALS * 4);
+    owned_score_bytes = ordered ? align256(yr_ngcf_owned_score_workspace_bytes(n, B)) : 0;
+    dw_slots_bytes = ordered && K > 0 ? align256(yr_ngcf_owned_dw_workspace_bytes(n, D)) : 0;
+    owned_score = at; at += owned_score_bytes;
+    dw_slots = at;    at += dw_slots_bytes;
     total = at;
   }
 };
@@ -106,10 +113,19 @@ struct StepLayout {
 
 using namespace yr;
 
-extern "C" int64_t yr_ngcf_step_workspace_bytes(int64_t n, int D, int K, int64_t B) {
+static int64_t step_workspace_bytes(int64_t n, int D, int K, int64_t B, bool ordered) {
   if (n <= 0 || n > 0x7fffffff || B < 0 || K < 0 || K >= YR_NGCF_MAX_LAYERS) return YR_ERR_BADARG;
   if (D != 16 && D != 32 && D != 64 && D != 128) return YR_ERR_UNSUPPORTED;
-  return StepLayout(n, D, K, B).total;
+  if (ordered && yr_ngcf_owned_score_workspace_bytes(n, B) < 0) return yr_ngcf_owned_score_workspace_bytes(n, B);
+  return StepLayout(n, D, K, B, ordered).total;
+}
+
+extern "C" int64_t yr_ngcf_step_workspace_bytes(int64_t n, int D, int K, int64_t B) {
+  return step_workspace_bytes(n, D, K, B, false);
+}
+
+extern "C" int64_t yr_ngcf_step_ordered_workspace_bytes(int64_t n, int D, int K, int64_t B) {
+  return step_workspace_bytes(n, D, K, B, true);
 }
 
 #define YR_TRY(call)            \
@@ -118,14 +134,15 @@ extern "C" int64_t yr_ngcf_step_workspace_bytes(int64_t n, int D, int K, int64_t
     if (rc_ != 0) return rc_;   \
   } while (0)
 
-extern "C" int yr_ngcf_bpr_step(const int32_t* rowptr, const int32_t* col, const float* val, int64_t n, int64_t nnz,
-                                const int32_t* heavy_rows, int64_t n_heavy, int heavy_threshold,
-                                int64_t num_users, float* const* params, float* const* exp_avg,
-                                float* const* exp_avg_sq, int K, int D, const int64_t* user, const int64_t* pos,
-                                const int64_t* neg, int64_t B, double lr, double step_size, double bc2_sqrt,
-                                double beta1, double beta2, double eps, double weight_decay, int mode,
-                                double subset_fraction, void* workspace, int64_t workspace_bytes, float* loss_out,
-                                double* loss_accum, int32_t* err_flag, void* stream) {
+// The step in both modes.  ordered: no float atomic anywhere — the row sets listed ascending (yr_ngcf_frontier_order), the
+// score gradient and dW by their owner passes, and the backward product of a restricted layer always the pull form.
+static int ngcf_step(bool ordered, const int32_t* rowptr, const int32_t* col, const float* val, int64_t n, int64_t nnz,
+                     const int32_t* heavy_rows, int64_t n_heavy, int heavy_threshold, int64_t num_users,
+                     float* const* params, float* const* exp_avg, float* const* exp_avg_sq, int K, int D,
+                     const int64_t* user, const int64_t* pos, const int64_t* neg, int64_t B, double lr,
+                     double step_size, double bc2_sqrt, double beta1, double beta2, double eps, double weight_decay,
+                     int mode, double subset_fraction, void* workspace, int64_t workspace_bytes, float* loss_out,
+                     double* loss_accum, int32_t* err_flag, void* stream) {
   if (n <= 0 || n > 0x7fffffff || nnz < 0 || num_users <= 0 || num_users >= n || B < 0 || K < 0 ||
       K >= YR_NGCF_MAX_LAYERS)
     return YR_ERR_BADARG;
@@ -135,7 +152,8 @@ extern "C" int yr_ngcf_bpr_step(const int32_t* rowptr, const int32_t* col, const
   for (int t = 0; t < 1 + 2 * K; ++t)
     if (!params[t] || !exp_avg[t] || !exp_avg_sq[t]) return YR_ERR_BADARG;
   if (B > 0 && (!user || !pos || !neg)) return YR_ERR_BADARG;
-  const StepLayout lay(n, D, K, B);
+  if (ordered && yr_ngcf_owned_score_workspace_bytes(n, B) < 0) return (int)yr_ngcf_owned_score_workspace_bytes(n, B);
+  const StepLayout lay(n, D, K, B, ordered);
   if (workspace_bytes < lay.total || ((uintptr_t)workspace & 255)) return YR_ERR_BADARG;
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
@@ -192,6 +210,8 @@ extern "C" int yr_ngcf_bpr_step(const int32_t* rowptr, const int32_t* col, const
     else
       YR_TRY(yr_ngcf_frontier_expand(rowptr, col, n, rows(k + 1), counts + k + 1, max_rows[k + 1], flags(k), rows(k),
                                      counts + k, 0, stream));
+    // the list decides which rows share a chunk of the weight gradient: ascending, not in arrival order
+    if (ordered) YR_TRY(yr_ngcf_frontier_order(flags(k), n, rows(k), counts + k, stream));
   }
 
   // ---- forward: K propagation layers, layer-sum scores, loss
@@ -233,7 +253,10 @@ extern "C" int yr_ngcf_bpr_step(const int32_t* rowptr, const int32_t* col, const
   for (int k = 0; k < K; ++k)
     if (sub[k]) { first_sub = k; break; }
   if (hipMemsetAsync(dlayer(0), 0, (size_t)((first_sub + 1) * nd), s) != hipSuccess) return (int)hipGetLastError();
-  if (B > 0)
+  if (B > 0 && ordered)
+    YR_TRY(yr_ngcf_owned_score_bwd(layer_ptrs, dlayer_ptrs, K + 1, user, pos, neg, g_pos, g_neg, B, D, num_users,
+                                   n - num_users, ws + lay.owned_score, lay.owned_score_bytes, err_flag, stream));
+  else if (B > 0)
     YR_TRY(yr_ngcf_score_bwd(layer_ptrs, dlayer_ptrs, K + 1, user, pos, neg, g_pos, g_neg, B, D, num_users,
                              n - num_users, err_flag, stream));
   for (int k = K - 1; k >= 0; --k) {
@@ -244,10 +267,14 @@ extern "C" int yr_ngcf_bpr_step(const int32_t* rowptr, const int32_t* col, const
     if (sub[k]) {
       // dZ is written on the layer's rows only.  Few rows: they scatter into their neighbours (cost = their
       // non-zeros).  Many: dZ is cleared first and the pull product adds zeros elsewhere.
-      const bool push = est_rows[k] * hop <= kPushMaxPairs;
+      const bool push = !ordered && est_rows[k] * hop <= kPushMaxPairs;
       if (!push && hipMemsetAsync(dZ, 0, (size_t)(n * D * 4), s) != hipSuccess) return (int)hipGetLastError();
-      YR_TRY(yr_ngcf_dense_bwd_weight_rows(dlayer(k + 1), layer(k + 1), layer(k), Zk(k), n, D, dW1, dW2, rows(k),
-                                           counts + k, max_rows[k], stream));
+      if (ordered)
+        YR_TRY(yr_ngcf_owned_dense_bwd_weight(dlayer(k + 1), layer(k + 1), layer(k), Zk(k), n, D, dW1, dW2, rows(k),
+                                              counts + k, max_rows[k], ws + lay.dw_slots, lay.dw_slots_bytes, stream));
+      else
+        YR_TRY(yr_ngcf_dense_bwd_weight_rows(dlayer(k + 1), layer(k + 1), layer(k), Zk(k), n, D, dW1, dW2, rows(k),
+                                             counts + k, max_rows[k], stream));
       YR_TRY(yr_ngcf_dense_bwd_data_rows(dlayer(k + 1), layer(k + 1), layer(k), Zk(k), W1T, W2T, n, D, dZ, dlayer(k),
                                          rows(k), counts + k, max_rows[k], stream));
       if (push)
@@ -260,7 +287,11 @@ extern "C" int yr_ngcf_bpr_step(const int32_t* rowptr, const int32_t* col, const
                                   below ? counts + k - 1 : nullptr, below ? max_rows[k - 1] : 0, stream));
       }
     } else {
-      YR_TRY(yr_ngcf_dense_bwd_weight(dlayer(k + 1), layer(k + 1), layer(k), Zk(k), n, D, dW1, dW2, stream));
+      if (ordered)
+        YR_TRY(yr_ngcf_owned_dense_bwd_weight(dlayer(k + 1), layer(k + 1), layer(k), Zk(k), n, D, dW1, dW2, nullptr,
+                                              nullptr, 0, ws + lay.dw_slots, lay.dw_slots_bytes, stream));
+      else
+        YR_TRY(yr_ngcf_dense_bwd_weight(dlayer(k + 1), layer(k + 1), layer(k), Zk(k), n, D, dW1, dW2, stream));
       YR_TRY(yr_ngcf_dense_bwd_data(dlayer(k + 1), layer(k + 1), layer(k), Zk(k), W1T, W2T, n, D, dZ, dlayer(k), stream));
       YR_TRY(yr_spmm_csr(rowptr, col, val, dZ, dlayer(k), n, D, 1, heavy_rows, n_heavy, heavy_threshold, stream));
     }
@@ -281,4 +312,32 @@ extern "C" int yr_ngcf_bpr_step(const int32_t* rowptr, const int32_t* col, const
                               nullptr, 2 * K, lr, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, mode, stream));
   }
   return launch_status();
+}
+
+#define YR_NGCF_STEP_ARGS                                                                                             \
+  rowptr, col, val, n, nnz, heavy_rows, n_heavy, heavy_threshold, num_users, params, exp_avg, exp_avg_sq, K, D, user, \
+      pos, neg, B, lr, step_size, bc2_sqrt, beta1, beta2, eps, weight_decay, mode, subset_fraction, workspace,        \
+      workspace_bytes, loss_out, loss_accum, err_flag, stream
+
+extern "C" int yr_ngcf_bpr_step(const int32_t* rowptr, const int32_t* col, const float* val, int64_t n, int64_t nnz,
+                                const int32_t* heavy_rows, int64_t n_heavy, int heavy_threshold,
+                                int64_t num_users, float* const* params, float* const* exp_avg,
+                                float* const* exp_avg_sq, int K, int D, const int64_t* user, const int64_t* pos,
+                                const int64_t* neg, int64_t B, double lr, double step_size, double bc2_sqrt,
+                                double beta1, double beta2, double eps, double weight_decay, int mode,
+                                double subset_fraction, void* workspace, int64_t workspace_bytes, float* loss_out,
+                                double* loss_accum, int32_t* err_flag, void* stream) {
+  return ngcf_step(false, YR_NGCF_STEP_ARGS);
+}
+
+extern "C" int yr_ngcf_bpr_step_ordered(const int32_t* rowptr, const int32_t* col, const float* val, int64_t n,
+                                        int64_t nnz, const int32_t* heavy_rows, int64_t n_heavy, int heavy_threshold,
+                                        int64_t num_users, float* const* params, float* const* exp_avg,
+                                        float* const* exp_avg_sq, int K, int D, const int64_t* user,
+                                        const int64_t* pos, const int64_t* neg, int64_t B, double lr,
+                                        double step_size, double bc2_sqrt, double beta1, double beta2, double eps,
+                                        double weight_decay, int mode, double subset_fraction, void* workspace,
+                                        int64_t workspace_bytes, float* loss_out, double* loss_accum,
+                                        int32_t* err_flag, void* stream) {
+  return ngcf_step(true, YR_NGCF_STEP_ARGS);
 }

@@ -293,7 +293,8 @@ def _ptr_array(tensors, what):
 
 class NGCFRowSet:
     """A set of graph nodes for the batch-aware propagation: ``flags`` int32[N] (1 = member), ``rows`` int32[N]
-    of which the first ``count[0]`` entries list the members in no particular order (the count stays on the device),
+    of which the first ``count[0]`` entries list the members in no particular order — ascending when the set was built
+    with ``ordered=True`` (the count stays on the device),
     ``max_rows`` the host's upper bound of the count (sizes grids only); ``push``: few rows — the backward product
     scatters from them (spmm_csr_push_rows)."""
     __slots__ = ("flags", "rows", "count", "max_rows", "push")
@@ -305,9 +306,16 @@ class NGCFRowSet:
         self.max_rows, self.push = int(min(max_rows, n)), bool(push)
 
 
-def ngcf_frontier_mark(num_users, num_items, user_id, pos_ids, neg_ids=None, max_rows=None, push=False):
+def _frontier_order(lib, out):
+    """The set's list rebuilt ascending from its flags (yr_ngcf_frontier_order): the same list in every run."""
+    check(lib.yr_ngcf_frontier_order(out.flags.data_ptr(), out.flags.numel(), out.rows.data_ptr(), out.count.data_ptr(),
+                                     _stream()), "yr_ngcf_frontier_order")
+    return out
+
+
+def ngcf_frontier_mark(num_users, num_items, user_id, pos_ids, neg_ids=None, max_rows=None, push=False, ordered=False):
     """The rows a batch's scores read — user_id, num_users + pos_ids, num_users + neg_ids (reference
-    models/ngcf.py:31-32,37-39) — as an NGCFRowSet."""
+    models/ngcf.py:31-32,37-39) — as an NGCFRowSet.  ``ordered``: the list ascending instead of in arrival order."""
     lib = _lib.load()
     i64 = torch.int64
     B = user_id.numel()
@@ -316,18 +324,19 @@ def ngcf_frontier_mark(num_users, num_items, user_id, pos_ids, neg_ids=None, max
                                     _dev(neg_ids, i64, "neg_ids") if (neg_ids is not None and B) else None, B,
                                     num_users, num_items, out.flags.data_ptr(), out.rows.data_ptr(), out.count.data_ptr(),
                                     1, _stream()), "yr_ngcf_frontier_mark")
-    return out
+    return _frontier_order(lib, out) if ordered else out
 
 
-def ngcf_frontier_expand(graph, rows, max_rows=None, push=False):
-    """The given NGCFRowSet plus all neighbours of its rows in the graph, as a new NGCFRowSet."""
+def ngcf_frontier_expand(graph, rows, max_rows=None, push=False, ordered=False):
+    """The given NGCFRowSet plus all neighbours of its rows in the graph, as a new NGCFRowSet (``ordered``: its list
+    ascending; the input's order never matters, only its members)."""
     lib = _lib.load()
     out = NGCFRowSet(graph.n, rows.flags.device, graph.n if max_rows is None else max_rows, push)
     check(lib.yr_ngcf_frontier_expand(_dev(graph.rowptr, torch.int32, "rowptr"), _dev(graph.col, torch.int32, "col"),
                                       graph.n, rows.rows.data_ptr(), rows.count.data_ptr(), rows.max_rows,
                                       out.flags.data_ptr(), out.rows.data_ptr(), out.count.data_ptr(), 1, _stream()),
           "yr_ngcf_frontier_expand")
-    return out
+    return _frontier_order(lib, out) if ordered else out
 
 
 def spmm_csr_subset(graph, X, out, row_active=None, accumulate=False, rows=None):
@@ -383,13 +392,54 @@ def ngcf_score(layers, num_users, user_id, pos_ids, neg_ids=None, err_flag=None)
     return pos if neg is None else (pos, neg)
 
 
-def ngcf_score_backward(layers, dlayers, num_users, user_id, pos_ids, neg_ids, gpos, gneg, err_flag=None):
-    """dlayers[k] += gradient of :func:`ngcf_score` w.r.t. layers[k] (float atomics)."""
+def ngcf_owned_score_workspace_bytes(n, B):
+    """Bytes of scratch :func:`ngcf_score_backward` needs with ``deterministic=True`` (EngineError for refused sizes)."""
+    v = int(_lib.load().yr_ngcf_owned_score_workspace_bytes(int(n), int(B)))
+    if v < 0:
+        check(v, "yr_ngcf_owned_score_workspace_bytes")
+    return v
+
+
+def ngcf_owned_dw_workspace_bytes(rows, d):
+    """Bytes of scratch :func:`ngcf_dense_bwd` needs with ``deterministic=True`` over at most ``rows`` rows."""
+    v = int(_lib.load().yr_ngcf_owned_dw_workspace_bytes(int(rows), int(d)))
+    if v < 0:
+        check(v, "yr_ngcf_owned_dw_workspace_bytes")
+    return v
+
+
+def _ngcf_scratch(workspace, nbytes, device, what):
+    if workspace is None:
+        return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < nbytes:
+        raise EngineError(f"{what}: workspace must be a contiguous uint8 tensor of at least {nbytes} bytes")
+    return workspace
+
+
+def ngcf_score_backward(layers, dlayers, num_users, user_id, pos_ids, neg_ids, gpos, gneg, err_flag=None,
+                        deterministic=False, workspace=None):
+    """dlayers[k] += gradient of :func:`ngcf_score` w.r.t. layers[k] (float atomics).  ``deterministic``: no float
+    atomics — every touched row of dlayers[k] is its content on entry plus the row's per-triplet contributions in
+    ascending triplet index (yr_ngcf_owned_score_bwd; ``workspace``: uint8 scratch of
+    :func:`ngcf_owned_score_workspace_bytes`, allocated when None)."""
     lib = _lib.load()
     n, d = layers[0].shape
     i64, f32 = torch.int64, torch.float32
     if len(layers) != len(dlayers):
         raise EngineError("layers / dlayers length mismatch")
+    if deterministic:
+        B = user_id.numel()
+        ws = _ngcf_scratch(workspace, ngcf_owned_score_workspace_bytes(n, B), layers[0].device, "ngcf_score_backward")
+        check(lib.yr_ngcf_owned_score_bwd(_ptr_array(layers, "layers"), _ptr_array(dlayers, "dlayers"), len(layers),
+                                          _dev(user_id, i64, "user_id") if B else None,
+                                          _dev(pos_ids, i64, "pos_ids") if B else None,
+                                          _dev(neg_ids, i64, "neg_ids") if (neg_ids is not None and B) else None,
+                                          _dev(gpos, f32, "gpos") if B else None,
+                                          _dev(gneg, f32, "gneg") if (neg_ids is not None and B) else None,
+                                          B, d, num_users, n - num_users, ws.data_ptr(), ws.numel(),
+                                          err_flag.data_ptr() if err_flag is not None else None, _stream()),
+              "yr_ngcf_owned_score_bwd")
+        return
     check(lib.yr_ngcf_score_bwd(_ptr_array(layers, "layers"), _ptr_array(dlayers, "dlayers"), len(layers),
                                 _dev(user_id, i64, "user_id"), _dev(pos_ids, i64, "pos_ids"),
                                 _dev(neg_ids, i64, "neg_ids") if neg_ids is not None else None,
@@ -416,11 +466,15 @@ def ngcf_dense_fwd(E, Z, W1, W2, out=None, rows=None):
     return out
 
 
-def ngcf_dense_bwd(dEout, Eout, E, Z, W1, W2, dE, dW1, dW2, dZ=None, W1T=None, W2T=None, rows=None):
+def ngcf_dense_bwd(dEout, Eout, E, Z, W1, W2, dE, dW1, dW2, dZ=None, W1T=None, W2T=None, rows=None,
+                   deterministic=False, workspace=None):
     """Backward of :func:`ngcf_dense_fwd`: dE += ..., dW1 += ..., dW2 += ..., returns dZ.
     ``W1T / W2T``: the transposed weights if the caller already has them (one batched transpose
     for all layers instead of two small launches per layer).  ``rows`` (NGCFRowSet): the rows outside it have
-    dEout = 0 and are skipped (their dZ is not written)."""
+    dEout = 0 and are skipped (their dZ is not written).  ``deterministic``: dW1 / dW2 without float atomics — the
+    workgroups' partial sums go to slots of ``workspace`` (uint8 scratch of :func:`ngcf_owned_dw_workspace_bytes`,
+    allocated when None) and are added to dW in workgroup order (yr_ngcf_owned_dense_bwd_weight); the data part has one
+    owner per output in both modes."""
     lib = _lib.load()
     n, d = E.shape
     f32 = torch.float32
@@ -428,6 +482,25 @@ def ngcf_dense_bwd(dEout, Eout, E, Z, W1, W2, dE, dW1, dW2, dZ=None, W1T=None, W
         dZ = torch.empty_like(E)
     if W1T is None:
         W1T, W2T = W1.t().contiguous(), W2.t().contiguous()  # [in, out] layout for the data-gradient GEMM
+    if deterministic:
+        bound = n if rows is None else rows.max_rows
+        ws = _ngcf_scratch(workspace, ngcf_owned_dw_workspace_bytes(bound, d), E.device, "ngcf_dense_bwd")
+        r, c, m = (None, None, 0) if rows is None else (rows.rows.data_ptr(), rows.count.data_ptr(), rows.max_rows)
+        check(lib.yr_ngcf_owned_dense_bwd_weight(_dev(dEout, f32, "dEout"), _dev(Eout, f32, "Eout"), _dev(E, f32, "E"),
+                                                 _dev(Z, f32, "Z"), n, d, _dev(dW1, f32, "dW1"), _dev(dW2, f32, "dW2"),
+                                                 r, c, m, ws.data_ptr(), ws.numel(), _stream()),
+              "yr_ngcf_owned_dense_bwd_weight")
+        if rows is not None:
+            check(lib.yr_ngcf_dense_bwd_data_rows(_dev(dEout, f32, "dEout"), _dev(Eout, f32, "Eout"), _dev(E, f32, "E"),
+                                                  _dev(Z, f32, "Z"), _dev(W1T, f32, "W1T"), _dev(W2T, f32, "W2T"), n, d,
+                                                  _dev(dZ, f32, "dZ"), _dev(dE, f32, "dE"), r, c, m, _stream()),
+                  "yr_ngcf_dense_bwd_data_rows")
+        else:
+            check(lib.yr_ngcf_dense_bwd_data(_dev(dEout, f32, "dEout"), _dev(Eout, f32, "Eout"), _dev(E, f32, "E"),
+                                             _dev(Z, f32, "Z"), _dev(W1T, f32, "W1T"), _dev(W2T, f32, "W2T"), n, d,
+                                             _dev(dZ, f32, "dZ"), _dev(dE, f32, "dE"), _stream()),
+                  "yr_ngcf_dense_bwd_data")
+        return dZ
     if rows is not None:
         r, c, m = rows.rows.data_ptr(), rows.count.data_ptr(), rows.max_rows
         check(lib.yr_ngcf_dense_bwd_weight_rows(_dev(dEout, f32, "dEout"), _dev(Eout, f32, "Eout"), _dev(E, f32, "E"),

@@ -9,6 +9,14 @@ trains the module's own parameters and the optimizer's own Adam state in place (
 checkpoints are unchanged), keeps the running loss on the device, and propagates layer k on the rows the batch's
 scores need when that set is small (``cfg.ngcf_subset_fraction``, see models/ngcf.py).  Results equal the autograd
 route's: the same kernels on the same data (tests/test_gpu_ngcf.py).
+
+``deterministic=True``: the step through ``yr_ngcf_bpr_step_ordered`` (csrc/ngcf_owned.hip) — no float atomics; the
+score gradient and dW are summed by the owners of their destinations in a fixed order, the batch's row sets are listed
+ascending and a restricted layer's backward product is always the pull form.  Two runs on the same batches give
+bit-identical parameters, Adam moments and losses (tests/test_gpu_ngcf_deterministic.py), as the reference's runs do
+under one seed; against the default mode the results differ by summation order only.  The mode exists in the fused
+step alone: SGD and ``fused_step=false`` go through autograd ops that add in arrival order, so the trainer and train.py
+refuse them (``DETERMINISTIC_NEEDS``) instead of running unordered.
 """
 import ctypes
 
@@ -17,11 +25,21 @@ import torch
 from . import _lib, engine, optim
 
 
+DETERMINISTIC_NEEDS = ("NGCF deterministic=True: the fused step (fused_step=true, NGCFStep) with optimizer adam or "
+                       "adamw; sgd and the autograd route (fused_step=false) sum gradients in arrival order")
+
+
+def deterministic_available(cfg):
+    """Can ``cfg`` (model_name NGCF) train with deterministic=true?  The conditions of NGCFTrainer._fused_step."""
+    return str(cfg.get("optimizer", "adam")).lower() in ("adam", "adamw") and bool(cfg.get("fused_step", True))
+
+
 class NGCFStep:
-    def __init__(self, model, optimizer, graph, subset_fraction=0.5):
+    def __init__(self, model, optimizer, graph, subset_fraction=0.5, deterministic=False):
         from . import optim
         if not isinstance(optimizer, optim.Adam):
-            raise NotImplementedError("NGCFStep: optimizer adam or adamw")
+            raise NotImplementedError(DETERMINISTIC_NEEDS if deterministic else "NGCFStep: optimizer adam or adamw")
+        self.deterministic = bool(deterministic)
         self.model, self.optimizer, self.graph = model, optimizer, graph
         self.subset_fraction = float(subset_fraction)
         self.params = [model.embedding.weight] + [w.weight for w in model.W1] + [w.weight for w in model.W2]
@@ -62,7 +80,9 @@ class NGCFStep:
 
     def _workspace(self, B):
         if self._ws is None or B > self._ws_batch:
-            nbytes = int(self._lib.yr_ngcf_step_workspace_bytes(self.n, self.D, self.K, B))
+            size = (self._lib.yr_ngcf_step_ordered_workspace_bytes if self.deterministic
+                    else self._lib.yr_ngcf_step_workspace_bytes)
+            nbytes = int(size(self.n, self.D, self.K, B))
             if nbytes < 0:
                 engine.check(nbytes, "yr_ngcf_step_workspace_bytes")
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.params[0].device)
@@ -83,14 +103,14 @@ class NGCFStep:
         t = int(st[0]["step"]) + 1
         b1, b2 = group["betas"]
         step_size, bc2_sqrt = engine.adam_scalars(t, group["lr"], b1, b2)
-        rc = self._lib.yr_ngcf_bpr_step(*self._graph_args, self.model.num_users, self._p, self._m, self._v, self.K,
-                                        self.D, u, p, n, B, group["lr"], step_size, bc2_sqrt, b1, b2, group["eps"],
-                                        group["weight_decay"],
-                                        engine.OPT_ADAMW if self.optimizer._decoupled else engine.OPT_ADAM,
-                                        self.subset_fraction, ws.data_ptr(), ws.numel(), self.loss.data_ptr(),
-                                        self.loss_accum.data_ptr(), self.flag.data_ptr(), engine._stream())
+        call = self._lib.yr_ngcf_bpr_step_ordered if self.deterministic else self._lib.yr_ngcf_bpr_step
+        rc = call(*self._graph_args, self.model.num_users, self._p, self._m, self._v, self.K, self.D, u, p, n, B,
+                  group["lr"], step_size, bc2_sqrt, b1, b2, group["eps"], group["weight_decay"],
+                  engine.OPT_ADAMW if self.optimizer._decoupled else engine.OPT_ADAM, self.subset_fraction,
+                  ws.data_ptr(), ws.numel(), self.loss.data_ptr(), self.loss_accum.data_ptr(), self.flag.data_ptr(),
+                  engine._stream())
         if rc:
-            engine.check(rc, "yr_ngcf_bpr_step")
+            engine.check(rc, "yr_ngcf_bpr_step_ordered" if self.deterministic else "yr_ngcf_bpr_step")
         for s in st:
             s["step"] = t
 

@@ -152,6 +152,10 @@ def train(cfg, args):
     from .trainers.ngcf_trainer import NGCFTrainer
     if cfg.model_name == 'S3Rec':
         return _train_s3rec(cfg, args)
+    if cfg.model_name == 'NGCF' and cfg.get("deterministic", False):
+        from .ngcf_step import DETERMINISTIC_NEEDS, deterministic_available
+        if not deterministic_available(cfg):                   # refused before training starts, never run unordered
+            raise NotImplementedError(DETERMINISTIC_NEEDS)
     if cfg.get("fast_loader") and cfg.model_name in ('MF', 'NGCF', 'DCN'):
         # device-side epoch sampler instead of DataLoader(MFDataset): same distribution, own RNG
         from .data.triplets import EpochLoader

@@ -6,7 +6,9 @@ Same constructor ``NGCFTrainer(cfg, num_items, num_users, laplacian_matrix)`` an
 NumPy RNG exactly like the reference (ngcf_trainer.py:140) — but propagates the graph once per
 call instead of once per sampled user.  With Adam / AdamW ``train`` runs every batch as ONE engine call
 (ngcf_step.NGCFStep: the launches of the autograd route, issued from C; cfg.fused_step=False keeps the reference's
-loop shape — bpr_forward, zero_grad, loss, backward, step — on the HIP autograd ops).
+loop shape — bpr_forward, zero_grad, loss, backward, step — on the HIP autograd ops).  ``cfg.deterministic=true``: the
+fused step without float atomics (NGCFStep(deterministic=True)): runs repeat bit for bit under one seed; where the
+fused step is not available (SGD, fused_step=false) ``train`` raises NotImplementedError instead of running unordered.
 
 Full-catalogue evaluation (new; the reference has only the 100-row sample): ``evaluate_full`` ranks the whole
 catalogue for EVERY row of the eval frame — one propagation, then the fused sweep over the layer tables
@@ -29,6 +31,10 @@ from .eval_set import EvalSets, _lists_to_csr, top_k_of_scores
 class NGCFTrainer(TripletTrainer):
     def __init__(self, cfg, num_items: int, num_users: int, laplacian_matrix) -> None:
         super().__init__(cfg)
+        if cfg.get("deterministic", False):
+            from ..ngcf_step import DETERMINISTIC_NEEDS, deterministic_available
+            if not deterministic_available(cfg):               # refused before a model is built, never run unordered
+                raise NotImplementedError(DETERMINISTIC_NEEDS)
         logger.info(f'[DEVICE] device = {self.device}')
         self.num_items = num_items
         self.num_users = num_users
@@ -42,13 +48,17 @@ class NGCFTrainer(TripletTrainer):
         """The whole batch step as one engine call (ngcf_step.NGCFStep) for Adam / AdamW unless
         cfg.fused_step is False; None -> the launch-by-launch autograd route below (SGD, or on request)."""
         from .. import optim
-        from ..ngcf_step import NGCFStep
+        from ..ngcf_step import DETERMINISTIC_NEEDS, NGCFStep
+        deterministic = bool(self.cfg.get("deterministic", False))
         if not isinstance(self.optimizer, optim.Adam) or not self.cfg.get("fused_step", True):
+            if deterministic:
+                raise NotImplementedError(DETERMINISTIC_NEEDS)     # the autograd route adds in arrival order
             return None
         graph = self.model.graph(self.laplacian_matrix)
         st = getattr(self, "_step", None)
-        if st is None or not st.bound_to(self.model, self.optimizer, graph):
-            st = self._step = NGCFStep(self.model, self.optimizer, graph, self.model._subset_fraction())
+        if st is None or st.deterministic != deterministic or not st.bound_to(self.model, self.optimizer, graph):
+            st = self._step = NGCFStep(self.model, self.optimizer, graph, self.model._subset_fraction(),
+                                       deterministic=deterministic)
         return st
 
     def train(self, train_dataloader) -> float:
