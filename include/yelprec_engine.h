@@ -225,6 +225,16 @@ int yr_bpr_mf_pull_apply(const float *U_old, float *U_new, float *I,
  * short.  Popularity is a property of the data set, so one order (e.g. from the train set's item degrees) serves
  * every step.  Results do not depend on it.  Ignored (as NULL) when the call covers only part of the item rows. */
 int yr_bpr_mf_pull_item_buckets(int64_t num_items, int D);
+/* Placement of the owner workgroups.  Workgroups are dealt round-robin over the 8 XCDs, each with an L2 of its own, so
+ * the owner slots s with equal s % 8 (one XCD's workgroups) take neighbouring buckets: runs of G consecutive buckets
+ * (G = 8 as built), run after run dealt over the eight classes.  Both calls run on the host.
+ * yr_bpr_mf_pull_owner_bucket: the bucket of owner slot `slot` when a pass covers nb buckets without a start order,
+ *   slot in [0, nb rounded up to a multiple of 8 G); -1 for a padded slot without a bucket, YR_ERR_BADARG outside.
+ * yr_bpr_mf_pull_item_start_order: the start order to pass as item_bucket_order, from the buckets' expected loads
+ *   (bucket_load_host[nb], host memory, no NaN): order_out[s] = the heaviest unused bucket of the class of slot s, and
+ *   the heaviest bucket left once that class is used up — a permutation of [0, nb), heaviest first in every class. */
+int yr_bpr_mf_pull_owner_bucket(int slot, int nb);
+int yr_bpr_mf_pull_item_start_order(const double *bucket_load_host, int nb, int32_t *order_out);
 /* yr_bpr_mf_pull_split_summary: which item buckets the partition in `workspace` shares between workgroups, for
  * tests and measurement scripts (valid once the user phase of yr_bpr_mf_pull_apply has run for the batch; the call
  * waits for `stream`).  counters_out[4] = {tile-range tasks, scratch slots, row tasks} the batch wants (word 3

@@ -91,6 +91,8 @@ SIGNATURES = {
     "yr_bpr_mf_pull_apply_ordered": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _int, _i64, _i64, _f,
                              _d, _d, _d, _d, _d, _d, _d, _int, _int, _p, _i64, _p, _p, _p, _int, _i64, _i64, _p, _p],
     "yr_bpr_mf_pull_item_buckets": [_i64, _int],
+    "yr_bpr_mf_pull_owner_bucket": [_int, _int],
+    "yr_bpr_mf_pull_item_start_order": [_p, _int, _p],
     "yr_bpr_mf_pull_split_summary": [_p, _i64, _i64, _int, _i64, _i64, _p, _p, _p, _p],
     "yr_loss_finalize": [_p, _f, _p, _p, _p],
     "yr_mf_scores_gemm": [_p, _p, _p, _i64, _int, _i64, _i64, _p, _i64, _p, _p],

@@ -217,7 +217,9 @@ class BPRMFStep:
         occurrences they receive per step, heaviest first (``item_weight``: anything proportional to the items'
         expected occurrences, e.g. the train set's item degrees + the uniform negatives' share; None: back to
         index order).  There are more item buckets than resident workgroups, so the late starters should be the
-        light ones; results do not depend on the order."""
+        light ones; results do not depend on the order.  The order is built by the engine
+        (``yr_bpr_mf_pull_item_start_order``): heaviest first inside every class of workgroup slots that share an
+        XCD, so that one L2 serves neighbouring buckets."""
         if item_weight is None:
             self._item_order = None
             return
@@ -227,7 +229,12 @@ class BPRMFStep:
         w = torch.zeros(nb * per, dtype=torch.float64, device=self.I.device)
         w[:self.I.shape[0]] = item_weight.to(self.I.device, torch.float64)
         load = w.view(nb, per).sum(1)
-        self._item_order = torch.argsort(load, descending=True, stable=True).to(torch.int32).contiguous()
+        # heaviest first inside every class of owner slots (slot % 8: the workgroups of one XCD keep neighbouring buckets)
+        load = load.cpu().contiguous()
+        order = torch.empty(nb, dtype=torch.int32)
+        engine.check(self._lib.yr_bpr_mf_pull_item_start_order(load.data_ptr(), nb, order.data_ptr()),
+                     "yr_bpr_mf_pull_item_start_order")
+        self._item_order = order.to(self.I.device)
 
     def _auto_item_order(self, p, n):
         # first pull step: the batch's own occurrence counts stand for the data set's item popularity

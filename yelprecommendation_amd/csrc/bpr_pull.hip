@@ -51,6 +51,7 @@
 // m, v and the Adam update stream 256 B per lane group and instruction.
 #include "adam.h"
 #include "common.h"
+#include "pull_placement.h"
 
 namespace yr {
 
@@ -65,6 +66,9 @@ constexpr int kOccShift = 26;                   // occ.x = user | local item row
 constexpr int kOccMask = (1 << kOccShift) - 1;
 constexpr int kMaxBuckets = 16383;              // (buckets + 1) * 4 B of dynamic LDS <= 64 KB
 constexpr int kMaxOwnerGrid = 4096;
+// which owner workgroup takes which bucket: owner_slots / owner_bucket of pull_placement.h
+static_assert(kMaxOwnerGrid % kXcdRound == 0 && YR_LOSS_PARTIALS % kXcdRound == 0,
+              "a capped grid strides by whole rounds of runs: ks += owners keeps owner_bucket a bijection");
 #ifndef YR_HEAVY_ROW
 #define YR_HEAVY_ROW 96
 #endif
@@ -89,6 +93,7 @@ constexpr int kSplitMin = YR_SPLIT_MIN;          // records of a bucket from whi
 constexpr int kSplitTarget = YR_SPLIT_TARGET;    // records per part (one chunk of the item pass)
 constexpr int kMaxParts = 64;
 constexpr int kMaxTasks = 512;                   // helper workgroups at the front of the item pass's grid
+static_assert(kMaxTasks % 8 == 0, "the owners behind the helpers keep slot % 8 == blockIdx.x % 8 (owner_bucket)");
 constexpr int kMaxSlots = 1024;                  // scratch slots of 1024 floats (one bucket's rows)
 // Heavy item buckets below that size (a few hundred buckets of two to three times the average one, whose owners end
 // the item pass long after the rest): the bucket's ROWS are shared out between S = 2 or 4 workgroups, the owner
@@ -307,6 +312,7 @@ struct OwnerArgs {
   int nb, T, tile_stride;    // buckets on this side, tiles, records per tile region
   int rows;                  // rows of the own table
   int bucket_begin, bucket_end;
+  int slots;                 // owner slots: bucket_end with an order, else owner_slots(bucket_end - bucket_begin)
   const int32_t* order;      // optional: workgroup slot -> bucket (a permutation of [0, nb): heaviest buckets first)
   int heavy_t;               // rows with more records in a chunk are walked by all four waves
   float inv_batch;
@@ -852,8 +858,8 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
 #endif
   YR_STAMP(0);
 
-  for (int ks = helper ? (int)blockIdx.x : a.bucket_begin + (int)blockIdx.x - hb;
-       helper ? ks == (int)blockIdx.x : ks < a.bucket_end; ks += owners) {
+  for (int ks = helper ? (int)blockIdx.x : (int)blockIdx.x - hb;
+       helper ? ks == (int)blockIdx.x : ks < a.slots; ks += owners) {
     // ---- bucket selection: which bucket k, which part of how many, and which tiles [t_begin, t_end) this trip works
     // on, for an owner, a tile-range helper and a row helper.  (inline: as a function with `int&` results, and with
     // only the pool rules or only the tile range lifted, the item forms changed by 87 to 2,970 lines, some to 64 VGPRs)
@@ -871,7 +877,8 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
     // prologue is a round trip to the L2 that the whole workgroup waits for)
     int4 cnt = make_int4(0, 0, 0, 0);
     if (!USER && a.split) cnt = *reinterpret_cast<const int4*>(a.split);
-    int k_own = ks;
+    // (slot -> bucket: the caller's start order, else owner_bucket: one XCD's workgroups on neighbouring buckets)
+    int k_own = a.bucket_begin + owner_bucket(ks);
     if (!helper && a.order) k_own = a.order[ks];
     const int c_tasks = __builtin_amdgcn_readfirstlane(cnt.x), c_slots = __builtin_amdgcn_readfirstlane(cnt.y);
     const int c_rows = __builtin_amdgcn_readfirstlane(cnt.z);
@@ -897,6 +904,7 @@ __global__ __launch_bounds__(kBlock, YR_OWNER_WAVES) void owner_pass_kernel(Owne
       if (k < a.bucket_begin || k >= a.bucket_end) break;       // void task, or a bucket of another item chunk
     } else {
       k = __builtin_amdgcn_readfirstlane(k_own);
+      if (k >= a.bucket_end) continue;                          // a padded slot: no bucket
     }
     if (!USER && a.split) {
       const int word = __builtin_amdgcn_readfirstlane(split_parts(a.split)[k]);
@@ -1343,6 +1351,7 @@ static int pull_apply_impl(const float* U_old, float* U_new, float* I, float* mU
     ua.loss_partials = loss_partials;
     ua.nb = p.nbU; ua.T = p.T; ua.tile_stride = p.tile; ua.rows = (int)nU;
     ua.bucket_begin = 0; ua.bucket_end = p.nbU;
+    ua.slots = owner_slots(p.nbU);
     ua.order = nullptr;
     ua.heavy_t = kHeavyRow; ua.inv_batch = inv_batch; ua.adam = adam;
     // the first build_blocks workgroups size the item buckets (oversize ones are shared out in the item pass)
@@ -1352,7 +1361,7 @@ static int pull_apply_impl(const float* U_old, float* U_new, float* I, float* mU
     ua.b_split_min = rule.split_min; ua.b_split_target = rule.split_target;
     ua.b_rowsplit_min = rule.row_min; ua.b_rowsplit_quad = rule.row_quad;
     ua.split = w + p.o_split;
-    const int gu = (p.nbU < YR_LOSS_PARTIALS ? p.nbU : YR_LOSS_PARTIALS) + ua.build_blocks;   // one loss-partial slot per owner
+    const int gu = (ua.slots < YR_LOSS_PARTIALS ? ua.slots : YR_LOSS_PARTIALS) + ua.build_blocks;   // one loss-partial slot per owner
     if (p.narrow_users && deterministic)
       hipLaunchKernelGGL((owner_pass_kernel<D, true, true, true, 1>), dim3(gu), dim3(kBlock), 0, s, ua);
     else if (p.narrow_users)
@@ -1374,11 +1383,15 @@ static int pull_apply_impl(const float* U_old, float* U_new, float* I, float* mU
     ia.bucket_end = (int)((item_end + (1 << p.shiftI) - 1) >> p.shiftI);
     // a start order is a permutation of ALL item buckets: used when the call covers all of them
     ia.order = (item_order && ia.bucket_begin == 0 && ia.bucket_end == p.nbI) ? item_order : nullptr;
+    ia.slots = ia.order ? ia.bucket_end : owner_slots(ia.bucket_end - ia.bucket_begin);
     ia.heavy_t = kHeavyRow; ia.inv_batch = inv_batch; ia.adam = adam;
     ia.helper_blocks = kMaxTasks;
-    ia.split = w + p.o_split;
+    // (an empty batch has no partition launch, so nothing has reset the counters where ITS plan puts the block: the
+    // words there are left over from an earlier batch, and a helper that took one for a task would update a whole
+    // bucket a second time next to its owner.  Without the block every bucket is whole and the helpers leave.)
+    ia.split = B > 0 ? w + p.o_split : nullptr;
     ia.scratch = (float*)(w + p.o_scratch);
-    int gi = ia.bucket_end - ia.bucket_begin;
+    int gi = ia.slots;
     if (gi > kMaxOwnerGrid) gi = kMaxOwnerGrid;
     gi += ia.helper_blocks;                       // helpers first: they start before the owners
     if (gradI_out && deterministic)
@@ -1400,6 +1413,22 @@ extern "C" int yr_bpr_mf_pull_item_buckets(int64_t num_items, int D) {
   if (num_items <= 0 || (D != 16 && D != 32 && D != 64 && D != 128)) return YR_ERR_BADARG;
   const int sh = bucket_shift(D);
   return (int)((num_items + (1 << sh) - 1) >> sh);
+}
+
+// The bucket of an owner slot over nb buckets (owner_bucket), -1 for a padded slot without one; host only.
+extern "C" int yr_bpr_mf_pull_owner_bucket(int slot, int nb) {
+  if (nb <= 0 || nb > kMaxBuckets || slot < 0 || slot >= owner_slots(nb)) return YR_ERR_BADARG;
+  const int k = owner_bucket(slot);
+  return k < nb ? k : -1;
+}
+
+// The item pass's start order for the buckets' expected loads (owner_start_order); host only.
+extern "C" int yr_bpr_mf_pull_item_start_order(const double* bucket_load_host, int nb, int32_t* order_out) {
+  if (!bucket_load_host || !order_out || nb <= 0 || nb > kMaxBuckets) return YR_ERR_BADARG;
+  for (int k = 0; k < nb; ++k)
+    if (!(bucket_load_host[k] == bucket_load_host[k])) return YR_ERR_BADARG;   // NaN: no order
+  owner_start_order(bucket_load_host, nb, order_out);
+  return 0;
 }
 
 // What build_splits decided for the partition in `workspace` (tests and measurement scripts; synchronises `stream`).
