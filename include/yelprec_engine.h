@@ -940,6 +940,61 @@ int yr_dcn_score(const float *Au, int64_t ldau, const float *Bi, int64_t ldbi, c
                  int L, int F, float *scores, int64_t row_stride, int32_t *err_flag, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * DCN, reproducible step (csrc/dcn_owned.hip).  The reference's runs repeat bit for bit under one seed
+ * (trainers/dcn_trainer.py:102-116); yr_dcn_head and yr_dcn_assemble_bwd add their gradients with float atomics.
+ * The entry points below issue no float atomic: every gradient element is summed by one owner in an order that is a
+ * pure function of the batch's ids and of the static item -> attribute table, and stored once.
+ *
+ * yr_dcn_head_ordered: yr_dcn_head (same arguments, limits and checks, both forms) plus a workspace of
+ *   yr_dcn_owned_head_workspace_bytes(units, F, H, L) bytes (a negative YR_ERR_* for refused shapes; needed only with
+ *   dx0 != NULL, 4-byte aligned, contents irrelevant on entry).  pred, loss_partials, dh and dx0 are yr_dcn_head's
+ *   bit for bit.  Weight gradients, with G = min(max(ceil(units / 4), 1), 256): wave w of workgroup g sums, from
+ *   0.0f, the terms of its units 4 g + w, 4 g + w + 4 G, ... in ascending order, the pos row of a unit before its neg
+ *   row (the terms yr_dcn_head hands to its accumulator, one f32 add each); the workgroup's value is
+ *   ((W0 + W1) + W2) + W3, stored into its slot; then dst = (((dst + P_0) + P_1) + ...) + P_{G-1} per element of
+ *   dcw / dcb / dWo / dbo.  units == 0: the gradients are not written.
+ * yr_dcn_owned_assemble_bwd: yr_dcn_assemble_bwd in the triplet form only (user, item_a = pos, item_b = neg all
+ *   given, attr_per_row == 0; YR_ERR_UNSUPPORTED otherwise), D = 16 / 32 / 64 / 128, row(b, pos) = b,
+ *   row(b, neg) = B + b.  Level 1, by id, entries in ascending key 4 b + role (user 0, pos 1, neg 2):
+ *     gU[u] = old, then per triplet b of the user: += dx[b, 0:D], then += dx[B + b, 0:D];
+ *     gI[i] = old + the item's rows' dx[row, D:2D]; from 0.0f, T_cat[i] = sum dx[row, 2D:3D], T_sc[i] = sum
+ *     dx[row, 3D:4D] (scratch).  Rows no triplet touches are not written.
+ *   Level 2, by attribute, over the inverted static table: cat_ptr [num_cats + 1] / cat_item / cat_mult — per category
+ *   its items in ascending order, each with the number m of its slots that name the category — and sc_ptr
+ *   [num_sc + 1] / sc_item; every list cut into chunks of YR_DCN_OWNED_CHUNK entries, cat_chunk_ptr / sc_chunk_ptr
+ *   [rows + 1] the running chunk counts (ceil(entries / YR_DCN_OWNED_CHUNK) per row), cat_chunks / sc_chunks their
+ *   totals.  A chunk's partial: from 0.0f, over its TOUCHED items (batch count != 0) in ascending item order,
+ *   += T_sc[i] (state-city) or += (float(m) * T_cat[i]) / float(Lmax) (category).  Destination row: old, then += the
+ *   partial of each of its chunks that has a touched item, in ascending chunk order.  Rows with no touched item are
+ *   not written.
+ *   Bad ids: a bad user raises YR_FLAG_BAD_USER and loses its user entry only; a bad item raises YR_FLAG_BAD_ITEM and
+ *   loses its item and attribute parts; an out-of-range slot of a valid item adds nothing (it is in no list) and
+ *   raises YR_FLAG_BAD_ITEM when that item is in the batch.
+ *   workspace: yr_dcn_owned_scatter_workspace_bytes(num_users, num_items, B, D, cat_chunks, sc_chunks) bytes (a
+ *   negative YR_ERR_* for refused sizes: 4 B + 2 must fit an int32), 16-byte aligned like dx / gU / gI (ldx a
+ *   multiple of 4), contents irrelevant on entry.  Checked before any launch: sizes (YR_ERR_BADARG), the width and
+ *   the form (YR_ERR_UNSUPPORTED), then B == 0: 0 (nothing is written), then null or misaligned pointers and a
+ *   workspace too small (YR_ERR_BADARG).
+ * ------------------------------------------------------------------------- */
+#define YR_DCN_OWNED_CHUNK 256
+int64_t yr_dcn_owned_head_workspace_bytes(int64_t units, int F, int H, int L);
+int yr_dcn_head_ordered(const float *x0, int64_t ldx, const float *h, int64_t ldh, int64_t units, int F, int H, int L,
+                        const float *cw, const float *cb, const float *Wo, const float *bo, int bpr, float inv_batch,
+                        float *pred, const float *gpred, float *dh, int64_t lddh, float *dx0, int64_t lddx,
+                        float *dcw, float *dcb, float *dWo, float *dbo, float *loss_partials,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+int64_t yr_dcn_owned_scatter_workspace_bytes(int64_t num_users, int64_t num_items, int64_t B, int D,
+                                             int64_t cat_chunks, int64_t sc_chunks);
+int yr_dcn_owned_assemble_bwd(const float *dx, int64_t ldx, const int32_t *cat_ids, const int32_t *sc_ids, int Lmax,
+                              int D, int64_t num_users, int64_t num_items, int64_t num_cats, int64_t num_sc,
+                              const int64_t *user, const int64_t *item_a, const int64_t *item_b, int64_t B,
+                              int attr_per_row, const int32_t *cat_ptr, const int32_t *cat_item,
+                              const int32_t *cat_mult, const int32_t *cat_chunk_ptr, int64_t cat_chunks,
+                              const int32_t *sc_ptr, const int32_t *sc_item, const int32_t *sc_chunk_ptr,
+                              int64_t sc_chunks, float *gU, float *gI, float *gC, float *gS,
+                              void *workspace, int64_t workspace_bytes, int32_t *err_flag, void *stream);
+
+/* ---------------------------------------------------------------------------
  * S3Rec scoring               (reference models/s3rec.py:53-115,184-214 in eval() mode; trainers/s3rec_trainer.py
  *   validate / evaluate call it through finetune / evaluate)
  * The self-attention encoder, forward only, one workgroup per sequence (csrc/s3rec.hip):

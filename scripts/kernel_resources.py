@@ -112,6 +112,17 @@ BUDGETS = [
      "ngcf_dense_bwd_weight_kernel with a store epilogue: the same body, so the same registers and 48 KB of LDS"),
     (r"void yr::ngcf_owned_dw_slots_kernel<128, (true|false)>", 512, 48 * 1024,
      "as above at D = 128: 8 output tiles per wave (128 accumulators), one wave per SIMD as the default kernel"),
+    # DCN training step, reproducible form (csrc/dcn_owned.hip; figures in profiles/dcn_owned_resources.txt)
+    (r"yr::dcn_head_kernel", 200, 38916,
+     "the default head: exactly what it compiled to before the ordered form shared its row loop (dcn_head_rows.h)"),
+    (r"yr::dcn_head_ordered_kernel", 256, 1024,
+     "the same row loop with a private accumulator per wave in DYNAMIC LDS (up to 155,664 B: one workgroup per CU at the "
+     "largest shape, five at the default one), so two waves per SIMD (512 / 2 -> 256) is all the registers have to allow"),
+    (r"yr::dcn_(head_reduce|owned_chunk|owned_attr_rows)_kernel", 64, 0,
+     "streaming sums in a fixed order, eight or sixteen loads ahead of their adds: eight waves per SIMD"),
+    (r"yr::dcn_owned_rows_kernel", 96, 0,
+     "a lane group per touched row, four entries' dx rows (three float4 each on an item row) ahead of their adds: five "
+     "waves per SIMD"),
 ]
 # Scratch (spilled registers) per lane.  The forms the benchmark and the trainers run by default — width 64, summation
 # order free — must have none; the deterministic-order forms and some forms of the other widths are held at 64 VGPRs by

@@ -137,6 +137,12 @@ SIGNATURES = {
                     _p, _p, _p, _p, _p, _p],
     "yr_dcn_score": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p, _p, _p, _p, _p, _p, _int, _int,
                      _p, _i64, _p, _p],
+    "yr_dcn_owned_head_workspace_bytes": [_i64, _int, _int, _int],
+    "yr_dcn_head_ordered": [_p, _i64, _p, _i64, _i64, _int, _int, _int, _p, _p, _p, _p, _int, _f, _p, _p, _p, _i64, _p,
+                            _i64, _p, _p, _p, _p, _p, _p, _i64, _p],
+    "yr_dcn_owned_scatter_workspace_bytes": [_i64, _i64, _i64, _int, _i64, _i64],
+    "yr_dcn_owned_assemble_bwd": [_p, _i64, _p, _p, _int, _int, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _int, _p, _p,
+                                  _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p],
     "yr_s3rec_encode": [_p, _p, _p, _p, _i64, _int, _int, _int, _int, _i64, _int, _p, _p, _p],
     "yr_s3rec_seq_scores": [_p, _p, _p, _p, _i64, _int, _i64, _p, _p, _p, _p],
     "yr_s3rec_candidate_scores": [_p, _p, _p, _p, _i64, _i64, _int, _i64, _p, _p, _p, _p],
@@ -163,7 +169,8 @@ RESTYPES.update({name: _i64 for name in (
     "yr_s3rec_catalogue_bce_workspace_floats", "yr_s3rec_catalogue_rank_workspace_bytes",
     "yr_cdae_catalogue_bce_workspace_floats", "yr_cdae_owned_workspace_bytes",
     "yr_ngcf_owned_score_workspace_bytes", "yr_ngcf_owned_dw_workspace_bytes",
-    "yr_ngcf_step_ordered_workspace_bytes")})
+    "yr_ngcf_step_ordered_workspace_bytes", "yr_dcn_owned_head_workspace_bytes",
+    "yr_dcn_owned_scatter_workspace_bytes")})
 
 _lib = None
 

@@ -17,15 +17,13 @@
 //   c_l = dz (W_oc . x0) + sum_{j>l} c_j (w_j . x0)        (scalars: one recursion)
 //   g_l = g_{l+1} + c_l w_l,   dx0 = g_0 + sum_l s_l g_{l+1},   dw_l += c_l x_l,   db_l += g_{l+1}.
 #include "common.h"
+#include "dcn_parts.h"
 
 namespace yr {
 
-
-constexpr int kDcnMaxF = 512;                 // 4 * D, D <= 128
-constexpr int kDcnMaxH = 1024;                // width of the last hidden layer
-constexpr int kDcnMaxL = 8;                   // cross orders
-constexpr int kDcnEF = kDcnMaxF / kWave;      // elements of an F-vector per lane
-constexpr int kDcnEH = kDcnMaxH / kWave;      // elements of an H-vector per lane
+// The limits live in dcn_parts.h (shared with csrc/dcn_owned.hip): kDcnMaxF = 512 (4 * D, D <= 128), kDcnMaxH = 1024
+// (width of the last hidden layer), kDcnMaxL = 8 (cross orders).
+static_assert(kDcnMaxF == 512 && kDcnMaxH == 1024 && kDcnMaxL == 8, "the comment above states the limits");
 
 // --------------------------------------------------------------------------- input assembly
 // Row r of x (B rows, or 2B with item_b: rows [0, B) pair user[b] with item_a[b], rows [B, 2B) with item_b[b]):
@@ -134,70 +132,7 @@ __global__ __launch_bounds__(kBlock) void relu_bwd_kernel(float* __restrict__ g,
     if (!(y[e] > 0.0f)) g[e] = 0.0f;
 }
 
-// --------------------------------------------------------------------------- cross-network constants
-// The row-independent parts of the closed form, computed by every wave for itself (L * F multiply-adds):
-//   bw[l] = beta_l . w_l,   boc = beta_L . W_oc + b_o,   beta[] = this lane's slice of beta_L.
-__device__ __forceinline__ void dcn_cross_consts(const float* __restrict__ cw, const float* __restrict__ cb,
-                                                 const float* __restrict__ Woc, const float* __restrict__ bo, int L,
-                                                 int F, int lane, float (&bw)[kDcnMaxL], float& boc,
-                                                 float (&beta)[kDcnEF]) {
-#pragma unroll
-  for (int j = 0; j < kDcnEF; ++j) beta[j] = 0.0f;
-#pragma unroll
-  for (int l = 0; l < kDcnMaxL; ++l) {
-    bw[l] = 0.0f;
-    if (l < L) {
-      float t = 0.0f;
-#pragma unroll
-      for (int j = 0; j < kDcnEF; ++j) {
-        const int e = lane + kWave * j;
-        if (e < F) {
-          t += beta[j] * cw[l * F + e];
-          beta[j] += cb[l * F + e];
-        }
-      }
-      bw[l] = wave_sum(t);
-    }
-  }
-  float t = 0.0f;
-#pragma unroll
-  for (int j = 0; j < kDcnEF; ++j) {
-    const int e = lane + kWave * j;
-    if (e < F) t += beta[j] * Woc[e];
-  }
-  boc = wave_sum(t) + bo[0];
-}
-
-__device__ __forceinline__ float sigmoidf(float z) { return 1.0f / (1.0f + expf(-z)); }
-
-// --------------------------------------------------------------------------- fused head
-// One wave per unit: a triplet (bpr: rows b and B + b, pos and neg side by side) or a row.  Forward:
-//   z = W_od . h + alpha_L (W_oc . x0) + boc,  pred = sigmoid(z),  loss += softplus(-(pred_pos - pred_neg)).
-// Backward (dx0 != NULL): dpred = the BPR gradient (inv_batch = 1 / B) or gpred[r]; dz = dpred pred (1 - pred);
-//   dh = dz W_od gated by h > 0 (h is the post-ReLU activation), dx0 = the cross part of d x0, and the weight
-//   gradients accumulated per workgroup in LDS, then added to dcw / dcb / dWo / dbo.
-struct DcnHead {
-  const float* x0;
-  int64_t ldx;
-  const float* h;
-  int64_t ldh;
-  int64_t units;
-  int F, H, L;
-  const float *cw, *cb, *Wo, *bo;
-  int bpr;
-  float inv_batch;
-  float* pred;
-  const float* gpred;
-  float* dh;
-  int64_t lddh;
-  float* dx0;
-  int64_t lddx;
-  float *dcw, *dcb, *dWo, *dbo;
-  float* loss_partials;
-};
-
-constexpr int kHeadAcc = (2 * kDcnMaxL + 1) * kDcnMaxF + kDcnMaxH + 1;
-
+// --------------------------------------------------------------------------- fused head (row loop: dcn_head_rows.h)
 __global__ __launch_bounds__(kBlock) void dcn_head_kernel(DcnHead p) {
   __shared__ float sAcc[kHeadAcc];             // [dcw: L*F | dcb: L*F | dWo: H + F | dbo]
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -206,153 +141,10 @@ __global__ __launch_bounds__(kBlock) void dcn_head_kernel(DcnHead p) {
   const int oDcb = L * F, oWo = 2 * L * F, oBo = 2 * L * F + H + F;
   if (grads)
     for (int e = threadIdx.x; e <= oBo; e += kBlock) sAcc[e] = 0.0f;
-  const float* Wod = p.Wo;
-  const float* Woc = p.Wo + H;
-  float bw[kDcnMaxL], boc, betaL[kDcnEF];
-  dcn_cross_consts(p.cw, p.cb, Woc, p.bo, L, F, lane, bw, boc, betaL);
-  __syncthreads();
-
-  float loss = 0.0f;
-  const int64_t rows_per_unit = p.bpr ? 2 : 1;
-  for (int64_t u = (int64_t)blockIdx.x * kWavesPerBlock + wave; u < p.units;
-       u += (int64_t)gridDim.x * kWavesPerBlock) {
-    float pr[2], q[2], pl[2][kDcnMaxL], sl[2][kDcnMaxL], al[2][kDcnMaxL + 1];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      pr[k] = q[k] = 0.0f;
-      if (k < rows_per_unit) {
-        const int64_t r = u + k * p.units;
-        const float* x = p.x0 + r * p.ldx;
-        const float* hr = p.h + r * p.ldh;
-        float xv[kDcnEF];
-        float tq = 0.0f, th = 0.0f;
-#pragma unroll
-        for (int j = 0; j < kDcnEF; ++j) {
-          const int e = lane + kWave * j;
-          xv[j] = e < F ? x[e] : 0.0f;
-          if (e < F) tq += xv[j] * Woc[e];
-        }
-#pragma unroll
-        for (int j = 0; j < kDcnEH; ++j) {
-          const int e = lane + kWave * j;
-          if (e < H) th += hr[e] * Wod[e];
-        }
-        float alpha = 1.0f;
-#pragma unroll
-        for (int l = 0; l < kDcnMaxL; ++l) {
-          al[k][l] = alpha;
-          pl[k][l] = sl[k][l] = 0.0f;
-          if (l < L) {
-            float t = 0.0f;
-#pragma unroll
-            for (int j = 0; j < kDcnEF; ++j) {
-              const int e = lane + kWave * j;
-              if (e < F) t += xv[j] * p.cw[l * F + e];
-            }
-            pl[k][l] = wave_sum(t);
-            sl[k][l] = alpha * pl[k][l] + bw[l];
-            alpha += sl[k][l];
-          }
-        }
-        al[k][kDcnMaxL] = alpha;
-        q[k] = wave_sum(tq);
-        const float z = wave_sum(th) + alpha * q[k] + boc;
-        pr[k] = sigmoidf(z);
-        if (p.pred && lane == 0) p.pred[r] = pr[k];
-      }
-    }
-    float dpred[2] = {0.0f, 0.0f};
-    if (p.bpr) {
-      const float d = pr[0] - pr[1];
-      loss += softplus_neg(d);
-      dpred[0] = -sigmoid_neg(d) * p.inv_batch;
-      dpred[1] = -dpred[0];
-    } else if (p.gpred) {
-      dpred[0] = p.gpred[u];
-    }
-    if (!grads) continue;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (k < rows_per_unit) {
-        const int64_t r = u + k * p.units;
-        const float dz = dpred[k] * pr[k] * (1.0f - pr[k]);
-        const float* hr = p.h + r * p.ldh;
-        float* dhr = p.dh + r * p.lddh;
-#pragma unroll
-        for (int j = 0; j < kDcnEH; ++j) {
-          const int e = lane + kWave * j;
-          if (e < H) {
-            const float hv = hr[e];
-            dhr[e] = hv > 0.0f ? dz * Wod[e] : 0.0f;
-            atomicAdd(&sAcc[oWo + e], dz * hv);
-          }
-        }
-        if (lane == 0) atomicAdd(&sAcc[oBo], dz);
-        const float alphaL = al[k][kDcnMaxL];
-        float c[kDcnMaxL];
-        float S = dz * q[k];
-#pragma unroll
-        for (int l = kDcnMaxL - 1; l >= 0; --l) {
-          c[l] = 0.0f;
-          if (l < L) {
-            c[l] = S;
-            S += c[l] * pl[k][l];
-          }
-        }
-        const float* x = p.x0 + r * p.ldx;
-        float xv[kDcnEF], G[kDcnEF], dx[kDcnEF];
-#pragma unroll
-        for (int j = 0; j < kDcnEF; ++j) {
-          const int e = lane + kWave * j;
-          xv[j] = e < F ? x[e] : 0.0f;
-          G[j] = e < F ? dz * Woc[e] : 0.0f;
-          dx[j] = 0.0f;
-          if (e < F) atomicAdd(&sAcc[oWo + H + e], dz * (alphaL * xv[j] + betaL[j]));
-        }
-#pragma unroll
-        for (int l = kDcnMaxL - 1; l >= 0; --l) {
-          if (l < L) {
-#pragma unroll
-            for (int j = 0; j < kDcnEF; ++j) {
-              const int e = lane + kWave * j;
-              if (e < F) {
-                dx[j] += sl[k][l] * G[j];
-                atomicAdd(&sAcc[oDcb + l * F + e], G[j]);
-                G[j] += c[l] * p.cw[l * F + e];
-              }
-            }
-          }
-        }
-        float* dxr = p.dx0 + r * p.lddx;
-#pragma unroll
-        for (int j = 0; j < kDcnEF; ++j) {
-          const int e = lane + kWave * j;
-          if (e < F) dxr[e] = dx[j] + G[j];
-        }
-        float bt[kDcnEF];
-#pragma unroll
-        for (int j = 0; j < kDcnEF; ++j) bt[j] = 0.0f;
-#pragma unroll
-        for (int l = 0; l < kDcnMaxL; ++l) {
-          if (l < L) {
-#pragma unroll
-            for (int j = 0; j < kDcnEF; ++j) {
-              const int e = lane + kWave * j;
-              if (e < F) {
-                atomicAdd(&sAcc[l * F + e], c[l] * (al[k][l] * xv[j] + bt[j]));
-                bt[j] += p.cb[l * F + e];
-              }
-            }
-          }
-        }
-      }
-    }
-  }
-  if (p.loss_partials) {
-    if (lane == 0) p.loss_partials[blockIdx.x * kWavesPerBlock + wave] = loss;
-    if (blockIdx.x == 0)
-      for (int e = gridDim.x * kWavesPerBlock + threadIdx.x; e < YR_LOSS_PARTIALS; e += kBlock) p.loss_partials[e] = 0.0f;
-  }
+  // terms into the workgroup's one accumulator, shared by its four waves: LDS float atomics (arrival order)
+#define DCN_HEAD_TERM(e, v) atomicAdd(&sAcc[e], v)
+#include "dcn_head_rows.h"
+#undef DCN_HEAD_TERM
   if (!grads) return;
   __syncthreads();
   for (int e = threadIdx.x; e <= oBo; e += kBlock) {

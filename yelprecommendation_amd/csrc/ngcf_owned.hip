@@ -36,6 +36,7 @@
 #include "common.h"
 #include "ngcf_parts.h"
 #include "owned_scan.h"
+#include "owned_triplets.h"
 
 #ifndef YR_NGCF_OWNED_DW_GRID
 #define YR_NGCF_OWNED_DW_GRID 256
@@ -44,80 +45,7 @@
 namespace yr {
 
 constexpr int kOwnedDwGrid = YR_NGCF_OWNED_DW_GRID;   // slots of the ordered weight gradient: one workgroup per CU
-constexpr int kRoleUser = 0, kRolePos = 1, kRoleNeg = 2;
-
-// ids of triplet b; false (and the flag bits) when one of them is out of range
-template <bool NEG>
-__device__ __forceinline__ bool owned_triplet(const int64_t* __restrict__ user, const int64_t* __restrict__ pos,
-                                              const int64_t* __restrict__ neg, int64_t b, int64_t num_users,
-                                              int64_t num_items, int64_t& u, int64_t& p, int64_t& n, int& bad) {
-  u = user[b]; p = pos[b]; n = NEG ? neg[b] : 0;
-  bool ok = true;
-  if (u < 0 || u >= num_users) { bad |= YR_FLAG_BAD_USER; ok = false; }
-  if (p < 0 || p >= num_items || n < 0 || n >= num_items) { bad |= YR_FLAG_BAD_ITEM; ok = false; }
-  return ok;
-}
-
-// cnt[row] = entries of the row; slot[3 b + role] = the entry's arrival number inside its row
-template <bool NEG>
-__global__ __launch_bounds__(kBlock) void ngcf_owned_count_kernel(const int64_t* __restrict__ user,
-                                                                  const int64_t* __restrict__ pos,
-                                                                  const int64_t* __restrict__ neg, int64_t B,
-                                                                  int64_t num_users, int64_t num_items,
-                                                                  int32_t* __restrict__ cnt, int32_t* __restrict__ slot,
-                                                                  int32_t* __restrict__ err_flag) {
-  int bad = 0;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; b < B; b += stride) {
-    int64_t u, p, n;
-    if (!owned_triplet<NEG>(user, pos, neg, b, num_users, num_items, u, p, n, bad)) continue;
-    slot[3 * b + kRoleUser] = atomicAdd(cnt + u, 1);
-    slot[3 * b + kRolePos] = atomicAdd(cnt + num_users + p, 1);
-    if (NEG) slot[3 * b + kRoleNeg] = atomicAdd(cnt + num_users + n, 1);
-  }
-  if (bad && err_flag) atomicOr(err_flag, bad);
-}
-
-template <bool NEG>
-__global__ __launch_bounds__(kBlock) void ngcf_owned_fill_kernel(const int64_t* __restrict__ user,
-                                                                 const int64_t* __restrict__ pos,
-                                                                 const int64_t* __restrict__ neg, int64_t B,
-                                                                 int64_t num_users, int64_t num_items,
-                                                                 const int32_t* __restrict__ start,
-                                                                 const int32_t* __restrict__ slot,
-                                                                 int32_t* __restrict__ ent) {
-  int bad = 0;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; b < B; b += stride) {
-    int64_t u, p, n;
-    if (!owned_triplet<NEG>(user, pos, neg, b, num_users, num_items, u, p, n, bad)) continue;
-    const int32_t key = (int32_t)(4 * b);
-    ent[start[u] + slot[3 * b + kRoleUser]] = key + kRoleUser;
-    ent[start[num_users + p] + slot[3 * b + kRolePos]] = key + kRolePos;
-    if (NEG) ent[start[num_users + n] + slot[3 * b + kRoleNeg]] = key + kRoleNeg;
-  }
-}
-
-// sorted[segment start + (number of smaller keys in the segment)] = key, a thread per entry
-__global__ __launch_bounds__(kBlock) void ngcf_owned_rank_kernel(const int64_t* __restrict__ user,
-                                                                 const int64_t* __restrict__ pos,
-                                                                 const int64_t* __restrict__ neg, int64_t num_users,
-                                                                 int64_t n_rows, const int32_t* __restrict__ start,
-                                                                 const int32_t* __restrict__ ent,
-                                                                 int32_t* __restrict__ sorted) {
-  const int64_t total = start[n_rows];
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e += stride) {
-    const int32_t key = ent[e];
-    const int64_t b = key >> 2;
-    const int role = key & 3;
-    const int64_t row = role == kRoleUser ? user[b] : num_users + (role == kRolePos ? pos[b] : neg[b]);
-    const int s0 = start[row], s1 = start[row + 1];
-    int rank = 0;
-    for (int j = s0; j < s1; ++j) rank += ent[j] < key;
-    sorted[s0 + rank] = key;
-  }
-}
+// the counting sort of the batch by destination row (count, fill, rank): owned_triplets.h
 
 constexpr int kOwnedAhead = 4;     // entries whose rows are loaded before the first of their adds
 

@@ -1442,12 +1442,95 @@ def dcn_assemble(U, I, C, S, attrs, user, item_a, item_b=None, attr_per_row=Fals
     return out
 
 
-def dcn_assemble_bwd(dx, attrs, user, item_a, item_b, gU, gI, gC, gS, num_users, attr_per_row=False, err_flag=None):
-    """Dense scatter-add of d x0 into the four table gradients (the category mean hands dx / Lmax to every slot)."""
+DCN_OWNED_CHUNK = 256        # YR_DCN_OWNED_CHUNK: entries per chunk of an inverted attribute list
+
+
+class DCNAttrLists:
+    """The item -> attribute table inverted for the ordered scatter (yr_dcn_owned_assemble_bwd): per category its items
+    in ascending order, each with the number of its slots that name the category (``cat_ptr`` [num_cats + 1],
+    ``cat_item``, ``cat_mult``), the same per state-city (``sc_ptr``, ``sc_item``), and the running chunk counts
+    ``cat_chunk_ptr`` / ``sc_chunk_ptr`` [rows + 1] of lists cut into chunks of DCN_OWNED_CHUNK entries.  int32 tensors;
+    slots and state-cities out of range are in no list."""
+    FIELDS = ("cat_ptr", "cat_item", "cat_mult", "cat_chunk_ptr", "sc_ptr", "sc_item", "sc_chunk_ptr")
+
+    def __init__(self, cat_ids, sc_ids, num_cats, num_sc, device=None, chunk=DCN_OWNED_CHUNK):
+        import numpy as np
+        cat = cat_ids.detach().cpu().numpy().astype(np.int64).reshape(len(sc_ids), -1)
+        sc = sc_ids.detach().cpu().numpy().astype(np.int64).reshape(-1)
+        ni, lmax = cat.shape
+        items = np.repeat(np.arange(ni, dtype=np.int64), lmax)
+        flat = cat.reshape(-1)
+        ok = (flat >= 0) & (flat < num_cats)
+        # (category, item) pairs with their multiplicity, ascending by category then item
+        pair, mult = np.unique(flat[ok] * ni + items[ok], return_counts=True)
+        self.num_cats, self.num_sc, self.num_items, self.Lmax, self.chunk = int(num_cats), int(num_sc), ni, lmax, int(chunk)
+        tables = {"cat_ptr": _list_ptr(pair // ni, num_cats), "cat_item": pair % ni, "cat_mult": mult}
+        ok = (sc >= 0) & (sc < num_sc)
+        it = np.flatnonzero(ok)
+        order = np.argsort(sc[it], kind="stable")                        # items stay ascending inside a state-city
+        tables.update(sc_ptr=_list_ptr(sc[it][order], num_sc), sc_item=it[order])
+        for k in ("cat", "sc"):
+            n = -(-np.diff(tables[k + "_ptr"]) // chunk)
+            tables[k + "_chunk_ptr"] = np.concatenate([[0], np.cumsum(n)])
+        self.cat_chunks, self.sc_chunks = int(tables["cat_chunk_ptr"][-1]), int(tables["sc_chunk_ptr"][-1])
+        for k in self.FIELDS:
+            t = torch.from_numpy(np.ascontiguousarray(tables[k]).astype(np.int32))
+            if t.numel() == 0:
+                t = torch.zeros(1, dtype=torch.int32)                    # never read: a list without entries
+            setattr(self, k, t.to(device) if device is not None else t)
+
+
+def _list_ptr(keys, rows):
+    import numpy as np
+    return np.concatenate([[0], np.cumsum(np.bincount(keys, minlength=rows))])
+
+
+def dcn_owned_head_workspace_bytes(units, F, H, L):
+    """Bytes of scratch :func:`dcn_head` needs with ``deterministic=True`` and gradients (EngineError when refused)."""
+    v = int(_lib.load().yr_dcn_owned_head_workspace_bytes(int(units), int(F), int(H), int(L)))
+    if v < 0:
+        check(v, "yr_dcn_owned_head_workspace_bytes")
+    return v
+
+
+def dcn_owned_scatter_workspace_bytes(num_users, num_items, B, D, lists):
+    """Bytes of scratch :func:`dcn_assemble_bwd` needs with ``deterministic=True`` for a batch of B triplets."""
+    v = int(_lib.load().yr_dcn_owned_scatter_workspace_bytes(int(num_users), int(num_items), int(B), int(D),
+                                                             lists.cat_chunks, lists.sc_chunks))
+    if v < 0:
+        check(v, "yr_dcn_owned_scatter_workspace_bytes")
+    return v
+
+
+def dcn_assemble_bwd(dx, attrs, user, item_a, item_b, gU, gI, gC, gS, num_users, attr_per_row=False, err_flag=None,
+                     deterministic=False, lists=None, workspace=None):
+    """Dense scatter-add of d x0 into the four table gradients (the category mean hands dx / Lmax to every slot).
+    ``deterministic``: no float atomics (yr_dcn_owned_assemble_bwd, the triplet form only) — every touched row is its
+    content on entry plus its contributions in the order of include/yelprec_engine.h; ``lists``: the
+    :class:`DCNAttrLists` of ``attrs`` (built when None), ``workspace``: uint8 scratch of
+    :func:`dcn_owned_scatter_workspace_bytes` (allocated when None)."""
     lib = _lib.load()
     cat_ids, sc_ids, num_cats, num_sc = attrs
     D = gI.shape[1]
     B = item_a.numel() if item_a is not None else dx.shape[0]
+    if deterministic:
+        if lists is None:
+            lists = DCNAttrLists(cat_ids, sc_ids, num_cats, num_sc, device=gI.device)
+        ws = _ngcf_scratch(workspace, dcn_owned_scatter_workspace_bytes(num_users, gI.shape[0], B, D, lists), gI.device,
+                           "dcn_assemble_bwd")
+        i32 = torch.int32
+        check(lib.yr_dcn_owned_assemble_bwd(
+            _rows(dx, torch.float32, "dx"), dx.stride(0), *_dcn_attr_args(attrs), D, int(num_users), gI.shape[0],
+            int(num_cats), int(num_sc), _opt(user, torch.int64, "user"), _opt(item_a, torch.int64, "item_a"),
+            _opt(item_b, torch.int64, "item_b"), B, 1 if attr_per_row else 0,
+            _dev(lists.cat_ptr, i32, "cat_ptr"), _dev(lists.cat_item, i32, "cat_item"),
+            _dev(lists.cat_mult, i32, "cat_mult"), _dev(lists.cat_chunk_ptr, i32, "cat_chunk_ptr"), lists.cat_chunks,
+            _dev(lists.sc_ptr, i32, "sc_ptr"), _dev(lists.sc_item, i32, "sc_item"),
+            _dev(lists.sc_chunk_ptr, i32, "sc_chunk_ptr"), lists.sc_chunks,
+            _opt(gU, torch.float32, "gU"), _dev(gI, torch.float32, "gI"), _dev(gC, torch.float32, "gC"),
+            _dev(gS, torch.float32, "gS"), ws.data_ptr(), ws.numel(), _opt(err_flag, torch.int32, "flag"), _stream()),
+            "yr_dcn_owned_assemble_bwd")
+        return
     check(lib.yr_dcn_assemble_bwd(_rows(dx, torch.float32, "dx"), dx.stride(0),
                                   *_dcn_attr_args(attrs), D, int(num_users),
                                   gI.shape[0], int(num_cats), int(num_sc), _opt(user, torch.int64, "user"),
@@ -1466,10 +1549,14 @@ def relu_bwd_(g, y):
     return g
 
 
-def dcn_head(x0, h, cw, cb, Wo, bo, bpr, inv_batch=0.0, pred=None, gpred=None, grads=None, loss_partials=None):
+def dcn_head(x0, h, cw, cb, Wo, bo, bpr, inv_batch=0.0, pred=None, gpred=None, grads=None, loss_partials=None,
+             deterministic=False, workspace=None):
     """Cross network + output layer + sigmoid (+ BPR loss) over the rows of x0 / h (yr_dcn_head).
     ``bpr``: rows [0, B) and [B, 2B) are the pos / neg rows of B triplets.  ``grads``: (dh, dx0, dcw, dcb, dWo, dbo)
-    — dh and dx0 are written, the weight gradients accumulated."""
+    — dh and dx0 are written, the weight gradients accumulated.  ``deterministic``: the weight gradients without float
+    atomics, summed per wave, per workgroup and over the workgroups in a fixed order (yr_dcn_head_ordered; everything
+    else comes out equal bit for bit); ``workspace``: uint8 scratch of :func:`dcn_owned_head_workspace_bytes`
+    (allocated when None)."""
     lib = _lib.load()
     f32 = torch.float32
     rows, F = x0.shape
@@ -1481,6 +1568,20 @@ def dcn_head(x0, h, cw, cb, Wo, bo, bpr, inv_batch=0.0, pred=None, gpred=None, g
     dh = dx0 = dcw = dcb = dWo = dbo = None
     if grads is not None:
         dh, dx0, dcw, dcb, dWo, dbo = grads
+    if deterministic:
+        ws = None
+        if grads is not None:
+            ws = _ngcf_scratch(workspace, dcn_owned_head_workspace_bytes(units, F, H, L), x0.device, "dcn_head")
+        check(lib.yr_dcn_head_ordered(
+            _rows(x0, f32, "x0"), x0.stride(0), _rows(h, f32, "h"), h.stride(0), units, F, H, L,
+            _dev(cw, f32, "cw"), _dev(cb, f32, "cb"), _dev(Wo, f32, "Wo"), _dev(bo, f32, "bo"),
+            1 if bpr else 0, float(inv_batch), _opt(pred, f32, "pred"), _opt(gpred, f32, "gpred"),
+            None if dh is None else _rows(dh, f32, "dh"), 0 if dh is None else dh.stride(0),
+            None if dx0 is None else _rows(dx0, f32, "dx0"), 0 if dx0 is None else dx0.stride(0),
+            _opt(dcw, f32, "dcw"), _opt(dcb, f32, "dcb"), _opt(dWo, f32, "dWo"), _opt(dbo, f32, "dbo"),
+            _opt(loss_partials, f32, "loss_partials"), None if ws is None else ws.data_ptr(),
+            0 if ws is None else ws.numel(), _stream()), "yr_dcn_head_ordered")
+        return
     check(lib.yr_dcn_head(_rows(x0, f32, "x0"), x0.stride(0), _rows(h, f32, "h"), h.stride(0), units, F, H, L,
                           _dev(cw, f32, "cw"), _dev(cb, f32, "cb"), _dev(Wo, f32, "Wo"), _dev(bo, f32, "bo"),
                           1 if bpr else 0, float(inv_batch), _opt(pred, f32, "pred"), _opt(gpred, f32, "gpred"),

@@ -52,6 +52,9 @@ class _DCNForward(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         model = ctx.model
+        if model.deterministic:
+            raise NotImplementedError("DCN: deterministic=true covers the fused training step (bpr_loss_backward); the "
+                                      "per-row attribute form of forward().backward() has no ordered scatter")
         user_id, item_id, attrs, x0, hs, pred = ctx.state
         params = model._param_list()
         grads = [torch.zeros_like(p) for p in params]
@@ -87,6 +90,10 @@ class DCN(BaseModel):
         self.sc_ids = None
         self._err_flag = None
         self._loss_partials = None
+        # deterministic: the training step sums every gradient in a fixed order (csrc/dcn_owned.hip: no float atomics)
+        self.deterministic = False
+        self._attr_lists = None
+        self._owned_ws = {}
 
     def _init_weights(self):
         # reference models/dcn.py:34-40: direct children only
@@ -103,6 +110,24 @@ class DCN(BaseModel):
         dev = self.user_embedding.weight.device
         self.cat_ids = cat_ids.to(dev, torch.int32).contiguous()
         self.sc_ids = sc_ids.to(dev, torch.int32).contiguous()
+        self._attr_lists = None
+
+    def _lists(self):
+        """The table inverted (category -> items, state-city -> items) for the ordered scatter: built on first use of
+        the deterministic mode, once per table."""
+        dev = self.user_embedding.weight.device
+        if self._attr_lists is None or self._attr_lists.cat_ptr.device != dev:
+            cats, sc, nc, ns = self._attrs()
+            self._attr_lists = engine.DCNAttrLists(cats, sc, nc, ns, device=dev)
+        return self._attr_lists
+
+    def _owned_workspace(self, which, nbytes):
+        """Cached uint8 scratch of the ordered kernels (contents irrelevant between calls), grown on demand."""
+        dev = self.user_embedding.weight.device
+        ws = self._owned_ws.get(which)
+        if ws is None or ws.device != dev or ws.numel() < nbytes:
+            ws = self._owned_ws[which] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        return ws
 
     def _linears(self):
         return [m for m in self.deep if isinstance(m, nn.Linear)]
@@ -179,8 +204,13 @@ class DCN(BaseModel):
     def _head(self, x0, hs, bpr, inv_batch=0.0, pred=None, gpred=None, grads=None, loss_partials=None):
         cw, cb = self._cross_packed()
         Wo, bo = self.output_layer.weight.detach(), self.output_layer.bias.detach()
+        ws = None
+        if self.deterministic and grads is not None:
+            units = x0.shape[0] // 2 if bpr else x0.shape[0]
+            ws = self._owned_workspace("head", engine.dcn_owned_head_workspace_bytes(units, x0.shape[1], hs[-1].shape[1],
+                                                                                     cw.shape[0]))
         engine.dcn_head(x0, hs[-1], cw, cb, Wo, bo, bpr, inv_batch=inv_batch, pred=pred, gpred=gpred, grads=grads,
-                        loss_partials=loss_partials)
+                        loss_partials=loss_partials, deterministic=self.deterministic, workspace=ws)
 
     def _rows_backward(self, user, item_a, item_b, attrs, attr_per_row, x0, hs, grads, gpred=None, pred=None,
                        inv_batch=0.0, loss_partials=None):
@@ -214,10 +244,16 @@ class DCN(BaseModel):
             else:
                 engine.gemm_f32(g, lin.weight.detach(), out=dx0, accumulate=True)
         C, S = self.attributes_embeddings[0].weight, self.attributes_embeddings[1].weight
+        lists = ws = None
+        if self.deterministic:
+            lists = self._lists()
+            ws = self._owned_workspace("scatter", engine.dcn_owned_scatter_workspace_bytes(
+                self.num_users, self.num_items, user.numel(), self.embed_size, lists))
         engine.dcn_assemble_bwd(dx0, attrs, user.contiguous(), item_a.contiguous(),
                                 None if item_b is None else item_b.contiguous(), grads[self.user_embedding.weight],
                                 grads[self.item_embedding.weight], grads[C], grads[S], self.num_users,
-                                attr_per_row=attr_per_row, err_flag=self._flag())
+                                attr_per_row=attr_per_row, err_flag=self._flag(), deterministic=self.deterministic,
+                                lists=lists, workspace=ws)
 
     # -- reference surface ---------------------------------------------------------------------
     def forward(self, user_id, item_id, *attributes):
@@ -231,11 +267,21 @@ class DCN(BaseModel):
         """model(u, p), model(u, n), BPRLoss and loss.backward() of reference dcn_trainer.py:102-116 for a batch:
         the pos and neg rows side by side through one gather, the deep tower GEMMs and one head kernel.  Gradients
         are ACCUMULATED into every parameter's dense ``.grad`` (allocated zero-filled on first use).  Returns the
-        batch-mean loss as a 1-element device tensor; ``loss_accum`` (float64[1]) also receives it."""
+        batch-mean loss as a 1-element device tensor; ``loss_accum`` (float64[1]) also receives it.
+        ``self.deterministic``: the ordered head and the ordered scatter (every GEMM of the tower already runs with
+        split_k = 1, one owner per output); an empty batch is then a step with a zero loss that adds nothing."""
         B = user_id.numel()
         scale = inv_batch if inv_batch is not None else (1.0 / B if B else 0.0)
         attrs = self._attrs()
         partials = self._partials()
+        if self.deterministic and B == 0:
+            if backward:
+                self._cross_grads()
+                for p in self.parameters():
+                    if p.grad is None:
+                        p.grad = torch.zeros_like(p)
+            partials.zero_()
+            return engine.loss_finalize(partials, 0.0, loss_out, loss_accum)
         x0, hs = self._rows_forward(user_id, pos_item, neg_item, attrs)
         if backward:
             self._cross_grads()

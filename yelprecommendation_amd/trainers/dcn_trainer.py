@@ -13,6 +13,8 @@ Differences underneath (results equal to float rounding):
 * ``evaluate`` scores all eval users against the whole catalogue with the fused scorer (yr_dcn_score) instead of one
   user at a time in chunks of ``batch_size`` items (dcn_trainer.py:145-165), then masks (``pred[mask] = 0``) and
   takes the top-n on the device.  Ties (the sigmoid saturates at 1.0f) are ordered by item id.
+* ``cfg.deterministic=true``: the training step sums every gradient in a fixed order (DCN.deterministic: no float
+  atomics), so a run repeats bit for bit under one seed — with any of the optimizers and either loader.
 """
 import torch
 
@@ -32,6 +34,8 @@ class DCNTrainer(TripletTrainer):
         self.num_users = num_users
         # built on the CPU under the seed (the reference's init order), then moved
         self.model = DCN(self.cfg, num_users, num_items, attributes_count).to(self.device)
+        # cfg.deterministic=true: the ordered head and scatter (csrc/dcn_owned.hip); Adam, AdamW and SGD are element-wise
+        self.model.deterministic = bool(self.cfg.get("deterministic", False))
         self.optimizer = self._optimizer(self.cfg.optimizer, self.model, self.cfg.lr, self.cfg.weight_decay)
         self.loss = self._loss()
         self.item2attributes = item2attributes
