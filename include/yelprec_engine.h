@@ -700,6 +700,35 @@ int yr_rank_metrics(const int64_t *topk, int64_t n, int k, const int64_t *pos_pt
                     const int64_t *pos_rows, double *workspace, double *out, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * The same metrics from the RANKS of the held-out items      (reference trainers/mf_trainer.py:134-178 and
+ *   metric.py:7-109: the four metrics are functions of the places of `actual` in the masked prediction, of the order
+ *   of `actual`, and of k — so one rank per held-out item gives them at every cutoff; csrc/metrics.hip)
+ *   rank [nnz] int64 from yr_catalogue_ranks, aligned with pos_idx: the 0-based place of entry e of row u's list
+ *   pos_ptr [n + 1] (-1: an id that was refused, never a hit).  ks [nk] int64 ON THE DEVICE, 1 <= nk <=
+ *   YR_METRICS_MAX_KS, every k >= 1 with no upper limit.  Entries of one row are distinct (the contract of
+ *   yr_catalogue_ranks), so |set(actual)| = len.
+ *   out (nk * YR_METRICS_PER_K + 6 float64):
+ *     out[ki * 12 + 0..9]  yr_rank_metrics' ten-vector at k = ks[ki], metric.py's quirks included: AP's numerator
+ *                          #{a < min(i, len) : rank[a] < i} at every hit place i = rank + 1, divided by len; DCG over
+ *                          places 1 .. min(len, k); recall's denominator len; empty rows skipped except by precision
+ *     out[ki * 12 + 10]    HR@k: the share of non-empty rows with at least one hit;  [11] its un-normalised sum
+ *     out[nk * 12 + 0]     MRR = mean over non-empty rows of 1 / (smallest rank + 1)
+ *     out[nk * 12 + 1]     AUC = mean, over the rows that have at least one (target, unmasked non-target) pair, of the
+ *                          share of such pairs in which the target comes first in the list order (ties by id, as
+ *                          everywhere).  Needs num_items >= 0 and the mask_ptr [n + 1] the ranks were taken under
+ *                          (NULL: nothing masked): with U = num_items - the row's mask count a target is masked exactly
+ *                          when rank >= U and then counts as behind every non-target; an unmasked one has
+ *                          rank - #(the row's targets ahead of it) non-targets ahead.  num_items < 0: NaN.
+ *     out[nk * 12 + 2..5]  the MRR sum, the AUC sum, the rows with a pair, the non-empty rows
+ *   workspace: yr_metrics_from_ranks_workspace_bytes(n, nk) bytes.  float64 sums in a fixed order.
+ * ------------------------------------------------------------------------- */
+#define YR_METRICS_PER_K 12
+#define YR_METRICS_MAX_KS 16
+int64_t yr_metrics_from_ranks_workspace_bytes(int64_t n, int nk);
+int yr_metrics_from_ranks(const int64_t *rank, int64_t n, const int64_t *pos_ptr, const int64_t *ks, int nk,
+                          int64_t num_items, const int64_t *mask_ptr, double *workspace, double *out, void *stream);
+
+/* ---------------------------------------------------------------------------
  * BPRLoss.forward / backward on score vectors        (reference loss.py:25-27)
  *   loss = mean_b( -logsigmoid(pos[b] - neg[b]) )  -> loss_partials (unscaled sums;
  *   finish with yr_loss_finalize(scale = 1/B));
@@ -1145,6 +1174,48 @@ int yr_s3rec_catalogue_rank(const float *H, const float *T, const int64_t *targe
                             const int64_t *excl_idx, const int64_t *excl_rows, int64_t N, int64_t R, int64_t K, int E,
                             int64_t first_col, int64_t *rank, float *target_score, void *workspace,
                             int64_t workspace_bytes, int32_t *err_flag, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Full-catalogue ranks of every held-out item: MF and NGCF   (reference trainers/mf_trainer.py:134-178 and
+ *   metric.py:7-109: per user, score the catalogue, pred[mask_items] = -3.40282e+38, sort, compare with `actual` —
+ *   here the places of the `actual` items in that sorted list, counted without the list; csrc/catalogue_rank.hip)
+ *   s(u, i) = sum_l <user_layers[l][u], item_layers[l][i]>,  l = 0 .. n_layers - 1 (1 .. YR_NGCF_MAX_LAYERS; both are
+ *   HOST arrays of device pointers to f32 tables [num_users][D] / [num_items][D], 16-byte aligned).  MF: one pair
+ *   (U, I).  NGCF: layer l is (E_l, E_l + num_users D).  One f32 accumulator started at 0, layers ascending, k
+ *   ascending inside a layer, on v_mfma_f32_32x32x2_f32: yr_s3rec_catalogue_rank's arithmetic, and for n_layers > 1
+ *   the order yr_ngcf_eval_topk documents.  D = 16, 32, 64, 128 (YR_ERR_UNSUPPORTED otherwise).
+ *   users [nrows] user ids (repeats allowed); pos_ptr [nrows + 1] / pos_idx [nnz]: the targets of each row in their
+ *   ORIGINAL order; mask_ptr [nrows + 1] / mask_idx: the masked items of each row, ids ascending inside a row (both
+ *   NULL: nothing masked).
+ *   rank [nnz] int64, aligned with pos_idx: the 0-based place of the target in the list order of its row — the
+ *   unmasked items by score descending then id ascending, then the masked items by id ascending:
+ *     unmasked target t:  #{ unmasked i != t : s_i > s_t, or s_i == s_t and i < t }
+ *     masked target t:    #(unmasked items) + #(masked ids below t)
+ *   The row's other targets are items like any other.  target_score [nnz] (may be NULL) = s(u, t).
+ *   A user id outside [0, num_users) raises YR_FLAG_BAD_USER and gives rank -1, score 0 to every target of the row;
+ *   a target outside [0, num_items) raises YR_FLAG_BAD_ITEM and gives rank -1, score 0; neither is dereferenced and
+ *   the other rows and targets are not disturbed.
+ *   Outside the contract (no pipeline produces them; the ranks are then unspecified, every access stays in bounds):
+ *   non-finite scores, duplicate entries inside one pos row, duplicate or descending entries inside one mask row.
+ * One arithmetic: a target's score comes from the same tile function as the swept scores, so an item row
+ * bit-identical to the target's ties exactly and the id decides; the target is excluded by id, never by score.
+ * Integers only in the reduction (lanes by shuffle and LDS integer adds, waves by LDS integer adds, chunks of 2,048
+ * items by per-chunk partials that a second kernel sums): a rank does not depend on nrows, on the row's place, on the
+ * other rows or on the grid; two calls give one answer bit for bit; no float atomics, no [nrows][num_items] array.
+ * A row tile owns 32 slots of up to YR_CATALOGUE_RANK_CAP targets of one row; rows with more targets take several.
+ * workspace: yr_catalogue_ranks_workspace_bytes(nrows, nnz, num_items, n_layers, D) bytes (a negative YR_ERR_* for
+ * refused sizes), 4-byte aligned, any contents.  Checked before any launch: negative sizes, D <= 0, n_layers outside
+ * 1 .. 8: YR_ERR_BADARG; the width, or nrows / num_items / slots beyond 32 bits: YR_ERR_UNSUPPORTED; then nrows == 0
+ * or nnz == 0: 0 (nothing is written); then an empty table, null or misaligned pointers, one half of the mask CSR
+ * without the other, a workspace too small: YR_ERR_BADARG.
+ * ------------------------------------------------------------------------- */
+#define YR_CATALOGUE_RANK_CAP 16
+int64_t yr_catalogue_ranks_workspace_bytes(int64_t nrows, int64_t nnz, int64_t num_items, int n_layers, int D);
+int yr_catalogue_ranks(const float *const *user_layers, const float *const *item_layers, int n_layers, int D,
+                       const int64_t *users, int64_t nrows, int64_t num_users, int64_t num_items,
+                       const int64_t *pos_ptr, const int64_t *pos_idx, int64_t nnz, const int64_t *mask_ptr,
+                       const int64_t *mask_idx, int64_t *rank, float *target_score, void *workspace,
+                       int64_t workspace_bytes, int32_t *err_flag, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Device-side S3Rec sequence batches  (reference data/datasets/s3rec_data_pipeline.py:13-50: split +

@@ -85,6 +85,18 @@ BUDGETS = [
      "four waves per SIMD (512 / 4 -> 128): more than the two workgroups per CU of the cbce kernel; no scratch"),
     (r"void yr::s3rec_rank_kernel<128>", 256, 1024, "as above at E = 128: 64 row registers, two waves per SIMD"),
     (r"yr::s3rec_rank_sum_kernel", 64, 0, "streaming integer sums of the chunks' counts"),
+    # MF / NGCF ranks of every held-out item (csrc/catalogue_rank.hip; figures in profiles/catalogue_rank_resources.txt)
+    (r"void yr::cr_sweep_kernel<(16|32|64), (true|false)>", 168, 7 * 1024,
+     "catalogue ranks: s3rec_rank_kernel's tile beside the slot's best / worst target and the binary search's "
+     "cursor; the 32 slots' sorted lists and integer bins in LDS (3 x 32 x 17 words); at least three waves per SIMD "
+     "(512 / 3 -> 168; 128 / 130 at D = 64); no scratch"),
+    (r"void yr::cr_sweep_kernel<128, (true|false)>", 256, 7 * 1024,
+     "as above at D = 128: 64 row registers (one table) or a layer's 64 at a time, two waves per SIMD"),
+    (r"void yr::cr_targets_kernel<(16|32|64|128), (true|false)>", 168, 5 * 1024,
+     "the targets' scores from the sweep's tile function and the rank sort of the slots' lists (2 x 32 x 17 words)"),
+    (r"yr::cr_(slots|finish)_kernel", 64, 2 * 1024, "integer scan of the rows' slot counts; integer sums of the bins"),
+    (r"yr::metrics_from_ranks(_sum|_finalize)?_kernel", 96, 2 * 1024,
+     "a wave per user over its ranks, float64 sums in a fixed order; the per-k columns live in dynamic LDS"),
     # CDAE without negative sampling: the catalogue BCE on the geometry of s3rec_cbce_kernel
     (r"void yr::cdae_cbce_kernel<(16|32|64), (true|false)>", 256, 9 * 1024,
      "CDAE plain BCE, catalogue sweep: the owned rows (H / 2 registers), their gradient (H / 2) and one tile of "

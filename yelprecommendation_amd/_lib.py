@@ -105,6 +105,8 @@ SIGNATURES = {
     "yr_topk_masked": [_p, _i64, _i64, _i64, _p, _p, _p, _f, _int, _p, _p],
     "yr_rank_metrics_workspace_bytes": [_i64],
     "yr_rank_metrics": [_p, _i64, _int, _p, _p, _p, _p, _p, _p],
+    "yr_metrics_from_ranks_workspace_bytes": [_i64, _int],
+    "yr_metrics_from_ranks": [_p, _i64, _p, _p, _int, _i64, _p, _p, _p, _p],
     "yr_bpr_loss_fwd": [_p, _p, _i64, _p, _p],
     "yr_bpr_loss_bwd": [_p, _p, _p, _f, _i64, _p, _p, _p],
     "yr_adam_dense": [_p, _p, _p, _p, _i64, _d, _d, _d, _d, _d, _d, _d, _int, _int, _p],
@@ -155,6 +157,8 @@ SIGNATURES = {
     "yr_s3rec_catalogue_bce": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _p, _p, _p, _p, _p, _i64, _p, _p],
     "yr_s3rec_catalogue_rank_workspace_bytes": [_i64, _i64, _int],
     "yr_s3rec_catalogue_rank": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _i64, _p, _p, _p, _i64, _p, _p],
+    "yr_catalogue_ranks_workspace_bytes": [_i64, _i64, _i64, _int, _int],
+    "yr_catalogue_ranks": [_p, _p, _int, _int, _p, _i64, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p],
     "yr_s3rec_batches": [_p, _p, _p, _p, _i64, _i64, _p, _i64, _int, _int, _int, C.c_uint64, C.c_uint64, _p, _p, _p, _p,
                          _p],
 }
@@ -170,7 +174,8 @@ RESTYPES.update({name: _i64 for name in (
     "yr_cdae_catalogue_bce_workspace_floats", "yr_cdae_owned_workspace_bytes",
     "yr_ngcf_owned_score_workspace_bytes", "yr_ngcf_owned_dw_workspace_bytes",
     "yr_ngcf_step_ordered_workspace_bytes", "yr_dcn_owned_head_workspace_bytes",
-    "yr_dcn_owned_scatter_workspace_bytes")})
+    "yr_dcn_owned_scatter_workspace_bytes", "yr_catalogue_ranks_workspace_bytes",
+    "yr_metrics_from_ranks_workspace_bytes")})
 
 _lib = None
 

@@ -214,9 +214,206 @@ __global__ __launch_bounds__(kBlock) void rank_metrics_finalize_kernel(const dou
   out[9] = (double)n;
 }
 
+// ---- the same metrics from the RANKS of the held-out items (yr_catalogue_ranks, csrc/catalogue_rank.hip) ----
+// rank[e] = the 0-based place of actual entry e in the user's whole prediction, so for every cutoff k at once
+//   hit(e, k)  = 0 <= rank[e] < k                        (rank -1: an id that was refused; never a hit)
+//   hits       = #hits;  precision = hits / k;  recall = hits / len        (no duplicates inside a row: the contract)
+//   AP         = sum over hits e of c(e) / (rank[e] + 1) / len,  c(e) = #{ a < min(rank[e] + 1, len) : 0 <= rank[a] <= rank[e] }
+//                — |set(actual[:i]) & set(pred[:i])| at i = rank[e] + 1, the reference's double truncation: the reason
+//                the ranks are kept in the ORIGINAL order of `actual`
+//   NDCG       = sum over e with rank[e] < span of 1 / log2(rank[e] + 2) over sum_{i <= span} 1 / log2(i + 1),
+//                span = min(len, k)
+//   HR         = 1 when hits > 0, averaged over the users with a non-empty list
+// and once per call, over the users with a non-empty list:
+//   MRR        = mean of 1 / (smallest rank + 1)                            (0 for a user without a valid rank)
+//   AUC        = mean, over the users that have at least one (target, unmasked non-target) pair, of the share of such
+//                pairs in which the target is ahead in the list order.  With U = the row's unmasked items (num_items -
+//                the length of its mask row), a target is masked exactly when rank >= U; an unmasked target has
+//                rank - #{the row's targets ahead of it} non-targets ahead of it, a masked one counts as behind all.
+// One WAVE per user: lanes stride over the entries, the two counts per entry (c(e) and the targets ahead) are loops
+// over the row shared by the wave.  float64, sums in a fixed order (wave butterfly, the workgroup's four waves in
+// order, then one thread per column over the workgroup partials).
+constexpr int kMfrPerK = 6;        // per cutoff: precision, recall, AP, NDCG, HR sums — and a spare
+constexpr int kMfrTail = 4;        // non-empty users, MRR sum, AUC sum, users with a pair
+
+__global__ __launch_bounds__(kBlock) void metrics_from_ranks_kernel(const int64_t* __restrict__ rank, int64_t n,
+                                                                     const int64_t* __restrict__ pos_ptr,
+                                                                     const int64_t* __restrict__ ks, int nk,
+                                                                     int64_t num_items,
+                                                                     const int64_t* __restrict__ mask_ptr,
+                                                                     double* __restrict__ partial) {
+  extern __shared__ double s_cols[];                   // [kWavesPerBlock][cols]
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int cols = nk * kMfrPerK + kMfrTail;
+  double* mine = s_cols + wave * cols;
+  const int64_t u = (int64_t)blockIdx.x * kWavesPerBlock + wave;
+  for (int c = lane; c < cols; c += kWave) mine[c] = 0.0;
+  if (u < n) {                                           // wave-uniform
+    const int64_t b = pos_ptr[u], len = pos_ptr[u + 1] - b;
+    const int64_t* rk = rank + b;
+    if (len > 0) {
+      const int64_t unmasked = num_items >= 0 ? num_items - (mask_ptr ? mask_ptr[u + 1] - mask_ptr[u] : 0) : -1;
+      // per entry of the lane: c(e) and the targets ahead; per wave: the best rank, the masked targets
+      int64_t best = -1, wrong = 0, n_masked = 0;
+      for (int64_t e0 = 0; e0 < len; e0 += kWave) {
+        const int64_t e = e0 + lane;
+        const int64_t re = e < len ? rk[e] : -1;
+        if (re >= 0) {
+          best = best < 0 || re < best ? re : best;
+          if (unmasked >= 0 && re >= unmasked) {
+            ++n_masked;
+          } else {
+            int64_t ahead = 0;
+            for (int64_t a = 0; a < len; ++a) {
+              const int64_t ra = rk[a];
+              ahead += (int64_t)(ra >= 0 && ra < re);
+            }
+            wrong += re - ahead;
+          }
+        }
+      }
+      for (int ki = 0; ki < nk; ++ki) {
+        const int64_t k = ks[ki];
+        const int64_t span = len < k ? len : k;
+        double hits = 0.0, ap = 0.0, dcg = 0.0, idcg = 0.0;
+        for (int64_t e0 = 0; e0 < len; e0 += kWave) {
+          const int64_t e = e0 + lane;
+          const int64_t re = e < len ? rk[e] : -1;
+          if (re >= 0 && re < k) {
+            hits += 1.0;
+            const int64_t na = re + 1 < len ? re + 1 : len;
+            int64_t c = 0;
+            for (int64_t a = 0; a < na; ++a) {
+              const int64_t ra = rk[a];
+              c += (int64_t)(ra >= 0 && ra <= re);
+            }
+            ap += (double)c / (double)(re + 1);
+            if (re < span) dcg += 1.0 / log2((double)(re + 2));
+          }
+        }
+        for (int64_t i = 1 + lane; i <= span; i += kWave) idcg += 1.0 / log2((double)(i + 1));
+        hits = wave_sum_f64(hits);
+        ap = wave_sum_f64(ap);
+        dcg = wave_sum_f64(dcg);
+        idcg = wave_sum_f64(idcg);
+        if (lane == 0) {
+          double* o = mine + ki * kMfrPerK;
+          o[0] = hits / (double)k;
+          o[1] = hits / (double)len;
+          o[2] = ap / (double)len;
+          o[3] = dcg / idcg;
+          o[4] = hits > 0.0 ? 1.0 : 0.0;
+        }
+      }
+      // the wave's best rank and pair counts (integers: exact in any order)
+#pragma unroll
+      for (int m = kWave / 2; m >= 1; m >>= 1) {
+        const int64_t ob = shfl_i64(best, lane ^ m);
+        best = ob >= 0 && (best < 0 || ob < best) ? ob : best;
+        wrong += shfl_i64(wrong, lane ^ m);
+        n_masked += shfl_i64(n_masked, lane ^ m);
+      }
+      if (lane == 0) {
+        double* o = mine + nk * kMfrPerK;
+        o[0] = 1.0;
+        o[1] = best >= 0 ? 1.0 / (double)(best + 1) : 0.0;
+        if (unmasked >= 0) {
+          int64_t valid = 0;                             // entries with a rank
+          for (int64_t a = 0; a < len; ++a) valid += (int64_t)(rk[a] >= 0);
+          const int64_t negatives = unmasked - (valid - n_masked);     // unmasked non-targets
+          if (negatives > 0) {
+            // an unmasked target is ahead of negatives - wrong(e) of them; a masked or refused one of none
+            const int64_t right = (valid - n_masked) * negatives - wrong;
+            o[2] = (double)right / ((double)len * (double)negatives);
+            o[3] = 1.0;
+          }
+        }
+      }
+    } else {
+      // precision counts every user, with 0 hits here: nothing to add
+    }
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < cols; c += kBlock) {
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < kWavesPerBlock; ++w) t += s_cols[w * cols + c];
+    partial[(int64_t)blockIdx.x * cols + c] = t;
+  }
+}
+
+// one workgroup per column of the partials: thread t sums rows t, t + 256, ... in order, thread 0 the 256 sums in order
+__global__ __launch_bounds__(kBlock) void metrics_from_ranks_sum_kernel(const double* __restrict__ partial,
+                                                                         int64_t nblocks, int cols,
+                                                                         double* __restrict__ sums) {
+  __shared__ double s_sum[kBlock];
+  const int c = blockIdx.x;
+  double s = 0.0;
+  for (int64_t b = threadIdx.x; b < nblocks; b += kBlock) s += partial[b * cols + c];
+  s_sum[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int t = 1; t < kBlock; ++t) s += s_sum[t];
+  sums[c] = s;
+}
+
+// out[ki * 12 + 0..9] = yr_rank_metrics' ten-vector at ks[ki], [10] = HR@k, [11] = its sum;
+// out[nk * 12 + 0..5] = MRR, AUC, the MRR sum, the AUC sum, the users with a pair, the users with a non-empty list
+__global__ void metrics_from_ranks_finalize_kernel(const double* __restrict__ sums, int nk, int64_t n,
+                                                   double* __restrict__ out) {
+  const int t = threadIdx.x;
+  const double* tail = sums + nk * kMfrPerK;
+  if (t < nk) {
+    const double* s = sums + t * kMfrPerK;
+    double* o = out + t * YR_METRICS_PER_K;
+    o[0] = s[0] / (double)n;
+    o[1] = s[1] / tail[0];
+    o[2] = s[2] / tail[0];
+    o[3] = s[3] / tail[0];
+    o[4] = tail[0];
+    o[5] = s[0]; o[6] = s[1]; o[7] = s[2]; o[8] = s[3];
+    o[9] = (double)n;
+    o[10] = s[4] / tail[0];
+    o[11] = s[4];
+  }
+  if (t == 0) {
+    double* o = out + nk * YR_METRICS_PER_K;
+    o[0] = tail[1] / tail[0];
+    o[1] = tail[2] / tail[3];
+    o[2] = tail[1];
+    o[3] = tail[2];
+    o[4] = tail[3];
+    o[5] = tail[0];
+  }
+}
+
 }  // namespace yr
 
 using namespace yr;
+
+extern "C" int64_t yr_metrics_from_ranks_workspace_bytes(int64_t n, int nk) {
+  if (n < 0 || nk < 1 || nk > YR_METRICS_MAX_KS) return YR_ERR_BADARG;
+  const int64_t cols = nk * kMfrPerK + kMfrTail;
+  return ((n + kWavesPerBlock - 1) / kWavesPerBlock + 1) * cols * (int64_t)sizeof(double);
+}
+
+extern "C" int yr_metrics_from_ranks(const int64_t* rank, int64_t n, const int64_t* pos_ptr, const int64_t* ks, int nk,
+                                     int64_t num_items, const int64_t* mask_ptr, double* workspace, double* out,
+                                     void* stream) {
+  if (n <= 0 || nk < 1 || nk > YR_METRICS_MAX_KS) return YR_ERR_BADARG;
+  if (!pos_ptr || !ks || !workspace || !out) return YR_ERR_BADARG;
+  const int64_t nblocks = (n + kWavesPerBlock - 1) / kWavesPerBlock;
+  if (nblocks > 0x7fffffff) return YR_ERR_BADARG;
+  const int cols = nk * kMfrPerK + kMfrTail;
+  hipStream_t s = (hipStream_t)stream;
+  double* sums = workspace + nblocks * cols;
+  hipLaunchKernelGGL(metrics_from_ranks_kernel, dim3((unsigned)nblocks), dim3(kBlock),
+                     kWavesPerBlock * cols * sizeof(double), s, rank, n, pos_ptr, ks, nk, num_items, mask_ptr,
+                     workspace);
+  hipLaunchKernelGGL(metrics_from_ranks_sum_kernel, dim3(cols), dim3(kBlock), 0, s, workspace, nblocks, cols, sums);
+  hipLaunchKernelGGL(metrics_from_ranks_finalize_kernel, dim3(1), dim3(kWave), 0, s, sums, nk, n, out);
+  return launch_status();
+}
 
 extern "C" int64_t yr_rank_metrics_workspace_bytes(int64_t n) {
   if (n < 0) return YR_ERR_BADARG;

@@ -1,6 +1,7 @@
-// The pieces the two S3Rec catalogue sweeps share (csrc/s3rec_pretrain.hip: the catalogue BCE; csrc/s3rec_rank.hip:
-// the catalogue rank): the tile geometry of the form that owns 32 rows and sweeps a table on v_mfma_f32_32x32x2_f32,
-// the accumulator layout, and the cursor over a row's ascending column list.
+// The pieces the catalogue sweeps share (csrc/s3rec_pretrain.hip: the catalogue BCE; csrc/s3rec_rank.hip: the rank of
+// one held-out item per sequence; csrc/catalogue_rank.hip: the ranks of every held-out item of MF and NGCF): the tile
+// geometry of the form that owns 32 rows and sweeps a table on v_mfma_f32_32x32x2_f32, the tile's arithmetic and
+// accumulator layout, and the cursor over a row's ascending column list.
 #pragma once
 #include "common.h"
 
@@ -37,5 +38,56 @@ __device__ __forceinline__ uint32_t cb_mask(const int64_t* __restrict__ idx, int
   }
   return m;
 }
+
+// ---- the rank sweeps' tile (csrc/s3rec_rank.hip, csrc/catalogue_rank.hip) ----
+// The lane's half of its owned row, k = 8 c + 4 hh + t at own[4 c + t] (hh = lane >> 5): the order of the swept rows'
+// 16-byte loads.  `row` points at element 4 hh of the row.
+template <int E>
+__device__ __forceinline__ void rank_own(float (&own)[E / 2], const float* __restrict__ row, bool ok) {
+#pragma unroll
+  for (int c = 0; c < E / 8; ++c) {
+    const float4 v = ok ? ld4(row + 8 * c) : zero4();
+    own[4 * c + 0] = v.x;
+    own[4 * c + 1] = v.y;
+    own[4 * c + 2] = v.z;
+    own[4 * c + 3] = v.w;
+  }
+}
+
+// acc[q] in lane j += <swept row cb_acc_row(q, lane), owned row j> over the E dims of one table, k ascending; `w` is
+// the lane's swept row + 4 (lane >> 5)
+template <int E>
+__device__ __forceinline__ f32x16 rank_tile_add(f32x16 acc, const float* __restrict__ w, bool ok,
+                                                const float (&own)[E / 2]) {
+#pragma unroll
+  for (int c = 0; c < E / 8; ++c) {
+    float4 wv = ld4(w + 8 * c);
+    if (!ok) wv = zero4();
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.x, own[4 * c + 0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.y, own[4 * c + 1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.z, own[4 * c + 2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.w, own[4 * c + 3], acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// one table: the accumulator starts at 0
+template <int E>
+__device__ __forceinline__ f32x16 rank_tile(const float* __restrict__ w, bool ok, const float (&own)[E / 2]) {
+  return rank_tile_add<E>(zero16(), w, ok, own);
+}
+
+// The diagonal of a tile whose swept row in lane r is a row chosen FOR owned row r (its target): the element of owned
+// row r = lane & 31 against swept row r sits in the half hh = (r >> 2) & 1 at q = (r & 3) + 4 (r >> 3).  Every lane
+// of the wave gets the value of its owned row.
+__device__ __forceinline__ float rank_diagonal(const f32x16& acc, int lane) {
+  const int r = lane & 31;
+  float ts = 0.0f;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) ts = cb_acc_row(q, lane) == r ? acc[q] : ts;
+  return __shfl(ts, r + 32 * ((r >> 2) & 1), kWave);
+}
+
+__device__ __forceinline__ uint32_t low_bits(int n) { return n >= 32 ? ~0u : (1u << n) - 1u; }   // n in [0, 32]
 
 }  // namespace yr

@@ -33,24 +33,7 @@ struct Rank {
   int32_t* err_flag;
 };
 
-// acc[q] in lane j = <swept row cb_acc_row(q, lane), owned row j>; `w` is the lane's swept row + 4 (lane >> 5)
-template <int E>
-__device__ __forceinline__ f32x16 rank_tile(const float* __restrict__ w, bool ok, const float (&own)[E / 2]) {
-  f32x16 acc = zero16();
-#pragma unroll
-  for (int c = 0; c < E / 8; ++c) {
-    float4 wv = ld4(w + 8 * c);
-    if (!ok) wv = zero4();
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.x, own[4 * c + 0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.y, own[4 * c + 1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.z, own[4 * c + 2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv.w, own[4 * c + 3], acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-__device__ __forceinline__ uint32_t low_bits(int n) { return n >= 32 ? ~0u : (1u << n) - 1u; }   // n in [0, 32]
-
+// rank_tile(), rank_own(), rank_diagonal() and low_bits(): s3rec_cb.h, shared with csrc/catalogue_rank.hip
 template <int E>
 __global__ __launch_bounds__(kBlock, E <= 64 ? 2 : 1) void s3rec_rank_kernel(Rank p) {
   __shared__ int32_t sC[kSweepTile];
@@ -68,14 +51,7 @@ __global__ __launch_bounds__(kBlock, E <= 64 ? 2 : 1) void s3rec_rank_kernel(Ran
 
     // the owned rows, k = 8 c + 4 hh + t at own[4 c + t]: the order of the swept rows' 16-byte loads
     float own[E / 2];
-#pragma unroll
-    for (int c = 0; c < E / 8; ++c) {
-      const float4 v = own_ok ? ld4(p.H + j * E + 8 * c + 4 * hh) : zero4();
-      own[4 * c + 0] = v.x;
-      own[4 * c + 1] = v.y;
-      own[4 * c + 2] = v.z;
-      own[4 * c + 3] = v.w;
-    }
+    rank_own<E>(own, p.H + j * E + 4 * hh, own_ok);
 
     const int64_t t_begin = chunk * (kSweepColChunk / kSweepTile) + (int64_t)wave * kSweepTilesPerWave;
     const int64_t t_end = std::min<int64_t>(t_begin + kSweepTilesPerWave, col_tiles);
@@ -97,15 +73,8 @@ __global__ __launch_bounds__(kBlock, E <= 64 ? 2 : 1) void s3rec_rank_kernel(Ran
       }
     }
 
-    // the diagonal tile: lane r sweeps T[target of owned row r]; the element of owned row r against its own target
-    // sits in the half hh = (r >> 2) & 1 at q = (r & 3) + 4 (r >> 3)
-    float ts = 0.0f;
-    {
-      const f32x16 acc = rank_tile<E>(p.T + (tgt >= 0 ? tgt : 0) * E + 4 * hh, tgt >= 0, own);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) ts = cb_acc_row(q, lane) == r ? acc[q] : ts;
-      ts = __shfl(ts, r + 32 * ((r >> 2) & 1), kWave);
-    }
+    // the diagonal tile: lane r sweeps T[target of owned row r] (rank_diagonal, s3rec_cb.h)
+    const float ts = rank_diagonal(rank_tile<E>(p.T + (tgt >= 0 ? tgt : 0) * E + 4 * hh, tgt >= 0, own), lane);
 
     int32_t cnt = 0;
     for (int64_t t = t_begin; t < t_end; ++t) {

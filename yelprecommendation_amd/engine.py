@@ -1326,6 +1326,115 @@ def rank_metrics(topk, pos_ptr, pos_idx, pos_rows=None):
     return out
 
 
+# ---- ranks of every held-out item against the catalogue (csrc/catalogue_rank.hip) and the metrics at any cutoff ----
+CATALOGUE_RANK_CAP = 16      # YR_CATALOGUE_RANK_CAP: targets per slot of the rank sweep
+SWEEP_TILE = 32              # csrc/s3rec_cb.h kSweepTile: rows (slots) per row tile, items per swept tile
+SWEEP_COL_CHUNK = 2048       # csrc/s3rec_cb.h kSweepColChunk: items per workgroup of the catalogue sweeps
+SWEEP_GRID_MAX = 2048        # csrc/s3rec_cb.h kSweepGridMax: workgroups per launch, the kernels loop from there
+METRICS_PER_K = 12           # YR_METRICS_PER_K
+METRICS_MAX_KS = 16          # YR_METRICS_MAX_KS
+
+
+def catalogue_rank_slots(pos_lengths):
+    """Slots the rank sweep cuts rows with these target counts into (ceil(len / CATALOGUE_RANK_CAP) each)."""
+    return sum(-(-int(n) // CATALOGUE_RANK_CAP) for n in pos_lengths)
+
+
+def catalogue_ranks(layers_user, layers_item, users, pos_ptr, pos_idx, mask_ptr, mask_idx_sorted, want_score=False,
+                    err_flag=None, out=None, score_out=None):
+    """rank [nnz] int64 of yr_catalogue_ranks, aligned with ``pos_idx``: the 0-based place of every held-out item
+    of row n (``pos_ptr`` / ``pos_idx``, original order) in the row's full prediction — the unmasked items by score
+    descending then id ascending, then the masked ones (``mask_ptr`` / ``mask_idx_sorted``, ids ascending inside a
+    row; both None: no mask) by id — what the reference's evaluation (trainers/mf_trainer.py:134-178, metric.py)
+    compares with ``actual``, for every cutoff at once.  Scores: the sum over the pairs
+    ``(layers_user[l] [num_users, D], layers_item[l] [num_items, D])`` of the dot products, one f32 accumulator, layers
+    ascending.  MF passes ``[U], [I]``; NGCF ``[E_l[:num_users]], [E_l[num_users:]]``.  -1 for a refused id
+    (``err_flag`` given: the bits are left there; else an IndexError).  ``want_score``: (rank, score [nnz] f32).
+    ``out`` / ``score_out``: the [nnz] buffers to write (exactly nnz entries are written)."""
+    lib = _lib.load()
+    f32, i64 = torch.float32, torch.int64
+    if len(layers_user) != len(layers_item):
+        raise EngineError("catalogue_ranks: one item-side table per user-side table")
+    pu, pi = _ptr_array(layers_user, "layers_user"), _ptr_array(layers_item, "layers_item")
+    nu, d = layers_user[0].shape
+    ni = layers_item[0].shape[0]
+    if any(tuple(t.shape) != (nu, d) for t in layers_user) or any(tuple(t.shape) != (ni, d) for t in layers_item):
+        raise EngineError("catalogue_ranks: tables must be [num_users, D] / [num_items, D] in every layer")
+    n, nnz = users.numel(), pos_idx.numel()
+    if pos_ptr.numel() != n + 1 or (mask_ptr is not None and mask_ptr.numel() != n + 1):
+        raise EngineError("catalogue_ranks: pos_ptr and mask_ptr hold rows + 1 entries")
+    if (mask_ptr is None) != (mask_idx_sorted is None):
+        raise EngineError("catalogue_ranks: mask_ptr and mask_idx come together")
+    if mask_idx_sorted is not None and mask_idx_sorted.numel() == 0:
+        mask_ptr = mask_idx_sorted = None              # every list empty: an empty tensor has no address to pass
+    dev = layers_user[0].device
+    ws_bytes = lib.yr_catalogue_ranks_workspace_bytes(n, nnz, ni, len(layers_user), d)
+    if ws_bytes < 0:
+        check(int(ws_bytes), "yr_catalogue_ranks_workspace_bytes")
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    rank = out if out is not None else torch.empty(nnz, dtype=i64, device=dev)
+    want_score = want_score or score_out is not None
+    score = score_out if score_out is not None else (torch.empty(nnz, dtype=f32, device=dev) if want_score else None)
+    if rank.numel() != nnz or (score is not None and score.numel() != nnz):
+        raise EngineError("catalogue_ranks: the output buffers hold one entry per entry of pos_idx")
+    flag = err_flag if err_flag is not None else new_error_flag(dev)
+    check(lib.yr_catalogue_ranks(pu, pi, len(layers_user), d, _dev(users, i64, "users"), n, nu, ni,
+                                 _dev(pos_ptr, i64, "pos_ptr"), _dev(pos_idx, i64, "pos_idx") if nnz else None, nnz,
+                                 _opt(mask_ptr, i64, "mask_ptr"), _opt(mask_idx_sorted, i64, "mask_idx"),
+                                 _dev(rank, i64, "rank") if nnz else None,
+                                 _dev(score, f32, "score") if want_score and nnz else None,
+                                 ws.data_ptr(), ws_bytes, _dev(flag, torch.int32, "err_flag"), _stream()),
+          "yr_catalogue_ranks")
+    if err_flag is None:
+        raise_on_flag(flag, "catalogue_ranks")
+    return (rank, score) if want_score else rank
+
+
+class RankMetrics(dict):
+    """``{k: (precision, recall, map, ndcg, hr)}`` with ``mrr`` and ``auc`` (also under those keys), ``raw`` the
+    float64 tensor of yr_metrics_from_ranks and ``ten(k)`` the ten-vector :func:`rank_metrics` returns at k."""
+
+    def ten(self, k):
+        i = self.ks.index(int(k))
+        return self.raw[i * METRICS_PER_K:i * METRICS_PER_K + 10]
+
+
+def metrics_from_ranks(rank, pos_ptr, ks, num_items=None, mask_ptr=None):
+    """precision / recall / MAP / NDCG / HR @k for every k of ``ks`` (each >= 1, no upper limit), MRR and AUC from the
+    ranks of the held-out items (:func:`catalogue_ranks`; ``pos_ptr`` [n + 1] the rows of ``rank``), with the quirks
+    of reference metric.py that :func:`rank_metrics` reproduces.  Definitions beyond the reference's four:
+    HR@k = the share of users with a non-empty list that have a hit among the first k; MRR = the mean over those users
+    of 1 / (their best rank + 1); AUC = the mean, over the users that have at least one (target, unmasked non-target)
+    pair, of the share of such pairs with the target ahead in the list order (ties by id; a masked target is behind
+    every non-target) — it needs ``num_items`` and the ``mask_ptr`` the ranks were taken under, and is NaN without.
+    -> :class:`RankMetrics`; one host sync."""
+    lib = _lib.load()
+    i64 = torch.int64
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= METRICS_MAX_KS or any(k < 1 for k in ks):
+        raise EngineError(f"metrics_from_ranks: 1 to {METRICS_MAX_KS} cutoffs, each at least 1")
+    n = pos_ptr.numel() - 1
+    dev = pos_ptr.device
+    if mask_ptr is not None and mask_ptr.numel() != n + 1:
+        raise EngineError("metrics_from_ranks: mask_ptr must have rows + 1 entries")
+    ws = torch.empty(lib.yr_metrics_from_ranks_workspace_bytes(n, len(ks)) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(len(ks) * METRICS_PER_K + 6, dtype=torch.float64, device=dev)
+    kt = torch.tensor(ks, dtype=i64, device=dev)
+    check(lib.yr_metrics_from_ranks(_dev(rank, i64, "rank") if rank.numel() else None, n, _dev(pos_ptr, i64, "pos_ptr"),
+                                    kt.data_ptr(), len(ks), -1 if num_items is None else int(num_items),
+                                    _opt(mask_ptr, i64, "mask_ptr"), ws.data_ptr(), out.data_ptr(), _stream()),
+          "yr_metrics_from_ranks")
+    host = out.tolist()
+    res = RankMetrics()
+    res.raw, res.ks = out, ks
+    for i, k in enumerate(ks):
+        v = host[i * METRICS_PER_K:(i + 1) * METRICS_PER_K]
+        res[k] = (v[0], v[1], v[2], v[3], v[10])
+    res.mrr = res["mrr"] = host[len(ks) * METRICS_PER_K]
+    res.auc = res["auc"] = host[len(ks) * METRICS_PER_K + 1]
+    return res
+
+
 def bpr_loss_fwd(pos, neg, loss_partials):
     """Partial sums of softplus(-(pos - neg))  (reference loss.py:25-27)."""
     lib = _lib.load()

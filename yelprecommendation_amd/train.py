@@ -203,7 +203,25 @@ def train(cfg, args):
                               args.data_pipeline.laplacian_matrix)
     trainer.run(train_dataloader, valid_dataloader, args.valid_eval_data)
     trainer.load_best_model()
-    return trainer, trainer.evaluate(args.test_eval_data, 'test')
+    if not (cfg.get("rank_eval") and cfg.model_name in ('MF', 'NGCF')):
+        return trainer, trainer.evaluate(args.test_eval_data, 'test')
+    # rank_eval: every cutoff of eval_ks from ONE rank sweep, with HR, MRR and AUC (logged); the return value stays the
+    # four figures at top_n
+    ks = cfg.get("eval_ks") or [cfg.top_n]
+    ks = [int(k) for k in (ks if isinstance(ks, (list, tuple)) else [ks])]
+    if cfg.model_name == 'NGCF' and not cfg.get("full_eval"):
+        # evaluate() is the reference's 100-row sample and does not look at rank_eval
+        result = trainer.evaluate(args.test_eval_data, 'test')
+        logger.info(f"[Trainer] full_eval is off: the figures above are the 100-row sample; rank evaluation of ALL "
+                    f"rows of the test frame follows, eval_ks={ks}")
+        trainer.evaluate_ranks(args.test_eval_data, ks=ks, mode='test')
+        return trainer, result
+    logger.info(f"[Trainer] rank evaluation of the test frame, eval_ks={ks}")
+    top_n = int(cfg.top_n)
+    res = trainer.evaluate_ranks(args.test_eval_data, ks=list(dict.fromkeys(ks + [top_n])), mode='test')
+    result = tuple(res[top_n][:4])
+    trainer._log_test(*result)
+    return trainer, result
 
 
 def _train_s3rec(cfg, args):

@@ -94,6 +94,22 @@ class BaseTrainer(ABC):
         logger.info(f"[Trainer] Test > precision@{self.cfg.top_n} : {p:.4f} / Recall@{self.cfg.top_n}: {r:.4f} / "
                     f"MAP@{self.cfg.top_n}: {m:.4f} / NDCG@{self.cfg.top_n}: {n:.4f}")
 
+    def _evaluate_ranks(self, layers_user, layers_item, eval_set, ks, mode):
+        """The rank route of MF and NGCF (``evaluate_ranks``): engine.catalogue_ranks over an EvalSets tuple whose
+        masks are sorted, then engine.metrics_from_ranks at every k of ``ks`` (default ``(cfg.top_n,)``)."""
+        ks = tuple(int(k) for k in (ks if ks is not None else (self.cfg.top_n,)))
+        users, mask_ptr, mask_idx, pos_ptr, pos_idx = eval_set[2:7]
+        rank = engine.catalogue_ranks(layers_user, layers_item, users.contiguous(), pos_ptr, pos_idx, mask_ptr,
+                                      mask_idx)
+        res = engine.metrics_from_ranks(rank, pos_ptr, ks, num_items=layers_item[0].shape[0], mask_ptr=mask_ptr)
+        if mode == 'test':
+            for k in ks:
+                p, r, m, n, h = res[k]
+                logger.info(f"[Trainer] Test > precision@{k} : {p:.4f} / Recall@{k}: {r:.4f} / MAP@{k}: {m:.4f} / "
+                            f"NDCG@{k}: {n:.4f} / HR@{k}: {h:.4f}")
+            logger.info(f"[Trainer] Test > MRR : {res.mrr:.4f} / AUC : {res.auc:.4f}")
+        return res
+
     def _accumulate(self, loss):
         # train_loss += loss.item() of the reference's loops without the per-step host sync
         p = getattr(self, "_partials", None)

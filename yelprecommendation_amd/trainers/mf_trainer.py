@@ -262,8 +262,28 @@ class MFTrainer(TripletTrainer):
             return self._hinted_topk(hint_key, U, I, users.contiguous(), mask_ptr, mask_idx)
         return engine.mf_recommend(U, I, users, mask_ptr, mask_idx, self.cfg.top_n, fused=False)
 
+    def evaluate_ranks(self, eval_data, ks=None, mode='valid'):
+        """``{k: (precision, recall, map, ndcg, hr)}`` for every k of ``ks`` (default ``(cfg.top_n,)``; any k >= 1)
+        plus ``mrr`` and ``auc`` (engine.metrics_from_ranks states them) over the eval frame: the rank of every
+        held-out item against the whole masked catalogue in one sweep (engine.catalogue_ranks), no top-k list and no
+        score matrix.  At a k the fused route takes, the four metrics equal :meth:`evaluate`'s."""
+        d = self.model.user_embedding.weight.shape[1]
+        if self.world_size > 1:
+            raise NotImplementedError("evaluate_ranks: user-sharded runs (world_size > 1) are not supported")
+        if d not in engine.SUPPORTED_WIDTHS:
+            raise NotImplementedError(f"evaluate_ranks: embedding width {d}; the rank sweep takes "
+                                      f"{engine.SUPPORTED_WIDTHS}")
+        self.model.eval()
+        U, I = self.model.user_embedding.weight.detach(), self.model.item_embedding.weight.detach()
+        return self._evaluate_ranks([U], [I], self._eval_set(eval_data), ks, mode)
+
     def evaluate(self, eval_data, mode='valid') -> tuple:
         # reference mf_trainer.py:134-161
+        if self.cfg.get("rank_eval", False):               # the same four figures at any top_n, by the rank sweep
+            p, r, m, n = self.evaluate_ranks(eval_data, (self.cfg.top_n,))[int(self.cfg.top_n)][:4]
+            if mode == 'test':
+                self._log_test(p, r, m, n)
+            return (p, r, m, n)
         self.model.eval()
         actual, users, mask_ptr, mask_idx = self._eval_arrays(eval_data)
         if self.world_size > 1:

@@ -165,9 +165,27 @@ class NGCFTrainer(TripletTrainer):
             self._log_test(p, r, m, n)
         return (p, r, m, n)
 
+    def evaluate_ranks(self, eval_data, ks=None, mode='valid'):
+        """``{k: (precision, recall, map, ndcg, hr)}`` for every k of ``ks`` (default ``(cfg.top_n,)``; any k >= 1)
+        plus ``mrr`` and ``auc`` over ALL rows of ``eval_data``: one propagation, then the rank of every held-out item
+        against the whole masked catalogue in one sweep over the layer tables (engine.catalogue_ranks, the layered
+        score of engine.ngcf_eval_topk), no top-k list and no score matrix.  Up to top_n = 16 the four metrics equal
+        :meth:`evaluate_full`'s."""
+        self.model.eval()
+        with torch.no_grad():
+            layers = self.model.propagate(self.laplacian_matrix)
+        nu = self.num_users
+        return self._evaluate_ranks([E[:nu] for E in layers], [E[nu:] for E in layers],
+                                    self._eval_sets.eval_set(eval_data, sort_masks=True), ks, mode)
+
     def evaluate(self, eval_data, mode='valid') -> tuple:
         # reference ngcf_trainer.py:134-165
         if self.cfg.get("full_eval", False):
+            if self.cfg.get("rank_eval", False):           # the same four figures at any top_n, by the rank sweep
+                p, r, m, n = self.evaluate_ranks(eval_data, (self.cfg.top_n,))[int(self.cfg.top_n)][:4]
+                if mode == 'test':
+                    self._log_test(p, r, m, n)
+                return (p, r, m, n)
             return self.evaluate_full(eval_data, mode)
         self.model.eval()
         positions = np.random.randint(eval_data.shape[0], size=100)            # :140, global NumPy RNG

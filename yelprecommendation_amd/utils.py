@@ -57,6 +57,10 @@ DEFAULTS = Config(
     # not in the reference: evaluate against the whole catalogue for every eval row — NGCF: evaluate() delegates to
     # evaluate_full() (all users instead of 100 sampled rows); S3Rec: evaluate_full() after the test evaluation
     full_eval=False,
+    # not in the reference: MF (and NGCF under full_eval) evaluate by the rank sweep — the exact rank of every held-out
+    # item, so the four metrics at ANY top_n (trainers' evaluate_ranks); eval_ks: the cutoffs train.py logs after the
+    # test evaluation with HR, MRR and AUC (None: top_n alone)
+    rank_eval=False, eval_ks=None,
     model=dict(
         CDAE=dict(negative_sampling=True, neg_times=5, hidden_size=64, corruption_level=0.6,
                   hidden_activation="sigmoid", output_activation="sigmoid"),
