@@ -25,6 +25,19 @@ def _declared_return_types():
             re.findall(r"^((?:const\s+)?\w+\s*\*?)\s*(yr_[a-z0-9_]+)\s*\(", hdr, flags=re.M)}
 
 
+_p, _i64, _int, _f, _d = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_double
+_u64, _i32 = ctypes.c_uint64, ctypes.c_int32
+PINNED_ARGTYPES = {
+    "yr_engine_version": [],
+    "yr_bpr_mf_pull_step": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _int, _i64, _i64, _f,
+                            _d, _d, _d, _d, _d, _d, _d, _int, _int, _p, _i64, _p, _p, _p, _p, _p],
+    "yr_triplet_sample": [_p, _p, _i64, _p, _p, _i64, _i64, _u64, _u64, _int, _i64, _i64, _p, _p, _p, _p, _p],
+    "yr_cdae_sparse_dwh": [_p, _p, _p, _p, _i64, _i64, _int, _p, _p, _p, _i32, _p, _p, _p],
+    "yr_ngcf_score_fwd": [_p, _int, _p, _p, _p, _i64, _int, _i64, _i64, _p, _p, _p, _p],      # const float *const *layers
+    "yr_catalogue_ranks_workspace_bytes": [_i64, _i64, _i64, _int, _int],
+}
+
+
 def test_library_exports_every_declared_symbol():
     """The C-ABI library loads and exports exactly what include/yelprec_engine.h declares
     (no compute calls here: there is no GPU in this container)."""
@@ -49,6 +62,100 @@ def test_library_exports_every_declared_symbol():
     assert lib.yr_engine_arch() == b"gfx950"
     raw = ctypes.CDLL(_lib.LIB_PATH)
     assert raw.yr_engine_version() == _lib.ENGINE_VERSION
+    # ... and with the argument types the header declares: these six, written out by hand, hold every scalar type of
+    # the ABI, a pointer-to-pointer argument, a (void) list and an int64_t return (a wrong one hands a kernel a
+    # truncated size or a garbage scalar)
+    for name, argtypes in PINNED_ARGTYPES.items():
+        assert _lib.SIGNATURES[name] == argtypes, name
+        assert list(getattr(lib, name).argtypes) == argtypes, name
+    assert {t for a in PINNED_ARGTYPES.values() for t in a} == {_p, _i64, _int, _f, _d, _u64, _i32}
+    assert lib.yr_catalogue_ranks_workspace_bytes.restype is _i64
+
+
+def _parse(text):
+    from yelprecommendation_amd import _lib
+    return _lib.parse_header(text)
+
+
+def test_parse_header_declarations():
+    """The header parser on short synthetic headers: a declaration over several lines, comments of both kinds that
+    hold something like a declaration, a pointer to pointers, (void) and an empty list, every scalar type."""
+    sigs, restypes, defines = _parse("""
+        /* yr_foo(int a) is no declaration, nor is
+           int yr_foo(int a); */
+        // int yr_bar(double x);
+        #define YR_X (-2)
+        #define YR_Y 7 /* #define YR_Z 1 */
+        #define YR_W 16   // trailing
+        #define YR_NOT_AN_INT 1.5f
+        #define OTHER_W 3
+        int yr_many(const float *const *layers, float *const* out,
+                    int64_t n, int d,   // int yr_inside(int a);
+                    uint64_t seed, int32_t part,
+                    float scale, double lr, const int64_t B,
+                    void *stream);
+        int64_t yr_size(void);
+        const char *yr_name();
+int yr_last(int);
+    """)
+    assert sigs == {"yr_many": [_p, _p, _i64, _int, _u64, _i32, _f, _d, _i64, _p], "yr_size": [], "yr_name": [],
+                    "yr_last": [_int]}
+    assert restypes == {"yr_size": _i64, "yr_name": ctypes.c_char_p}
+    assert defines == {"YR_X": -2, "YR_Y": 7, "YR_W": 16}
+
+
+@pytest.mark.parametrize("decl, named", [
+    ("int yr_bad(unsigned n);", "yr_bad"),                       # an unknown scalar: no guessing
+    ("int yr_bad(int64_t n, size_t bytes);", "yr_bad"),
+    ("int yr_bad(long long n);", "yr_bad"),
+    ("int yr_bad(int shape[4]);", "yr_bad"),
+    ("size_t yr_bad(void);", "yr_bad"),                          # ... or return type
+    ("float *yr_bad(void);", "yr_bad"),
+    ("int yr_ok(void); static inline int f(void) { return yr_hidden(3); }", "yr_hidden"),   # not at a line start
+])
+def test_parse_header_refuses_what_it_does_not_know(decl, named):
+    from yelprecommendation_amd._lib import EngineError
+    with pytest.raises(EngineError, match=named):
+        _parse(decl)
+
+
+def test_missing_header_fails_loudly(monkeypatch, tmp_path):
+    """No fallback table: without the header the binding cannot be read, and the error names the path."""
+    from yelprecommendation_amd import _lib
+    missing = os.path.join(str(tmp_path), "include", "yelprec_engine.h")
+    monkeypatch.setattr(_lib, "HEADER_PATH", missing)
+    with pytest.raises(_lib.EngineError, match=re.escape(missing)):
+        _lib._read_header()
+
+
+def test_constants_come_from_the_header():
+    """DEFINES, which the Python names of the header's constants read, holds every integer YR_* of the header."""
+    from yelprecommendation_amd import _lib, engine
+    hdr = open(os.path.join(ROOT, "include", "yelprec_engine.h")).read()
+    written = dict(re.findall(r"^#define (YR_\w+)\s+\(?(-?\d+)\)?", hdr, flags=re.M))
+    assert _lib.DEFINES == {k: int(v) for k, v in written.items()} and len(written) >= 27
+    assert (_lib.DEFINES["YR_ERR_UNSUPPORTED"], _lib.DEFINES["YR_ERR_BADARG"]) == (-1, -2)
+    assert engine.LOSS_PARTIALS == _lib.DEFINES["YR_LOSS_PARTIALS"] == 2048
+    assert engine.EVAL_FORMS["four_waves"] == _lib.DEFINES["YR_EVAL_FOUR_WAVES"]
+
+
+def test_size_query_raises_for_a_refused_size():
+    """Every *_workspace_bytes / _floats / _planes_bytes wrapper goes through one helper that turns the negative
+    YR_ERR_* of a refused shape into EngineError (rank_metrics and metrics_from_ranks used to hand it to torch.empty)."""
+    from yelprecommendation_amd import _lib, engine
+    lib = _lib.load()
+    assert lib.yr_rank_metrics_workspace_bytes(-1) == -2 and lib.yr_metrics_from_ranks_workspace_bytes(4, 17) == -2
+    with pytest.raises(_lib.EngineError, match="yr_rank_metrics_workspace_bytes: bad argument"):
+        _lib.query_size("yr_rank_metrics_workspace_bytes", -1)
+    with pytest.raises(_lib.EngineError, match="yr_metrics_from_ranks_workspace_bytes: bad argument"):
+        _lib.query_size("yr_metrics_from_ranks_workspace_bytes", 4, 17)
+    with pytest.raises(_lib.EngineError, match="unsupported configuration"):
+        _lib.query_size("yr_bpr_mf_pull_workspace_bytes", 10, 10, 10, 48)
+    with pytest.raises(_lib.EngineError, match="bad argument"):
+        engine.ngcf_owned_dw_workspace_bytes(-1, 64)
+    n = _lib.query_size("yr_rank_metrics_workspace_bytes", 100)
+    assert type(n) is int and n == lib.yr_rank_metrics_workspace_bytes(100) > 0
+    assert engine.cdae_owned_workspace_bytes(8, 100, 64) == lib.yr_cdae_owned_workspace_bytes(8, 100, 64) > 0
 
 
 def test_header_version_matches_binding():

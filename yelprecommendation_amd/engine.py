@@ -9,12 +9,13 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from ._lib import EngineError, check
+from ._lib import DEFINES, EngineError, check, query_size
 
-LOSS_PARTIALS = 2048        # YR_LOSS_PARTIALS
-FLAG_BAD_USER, FLAG_BAD_ITEM = 1, 2
-OPT_ADAM, OPT_ADAMW = 0, 1
-PULL_USER_PHASE, PULL_ITEM_PHASE = 1, 2
+# the header's #define values under their Python names (include/yelprec_engine.h is the one place they are written)
+LOSS_PARTIALS = DEFINES["YR_LOSS_PARTIALS"]
+FLAG_BAD_USER, FLAG_BAD_ITEM = DEFINES["YR_FLAG_BAD_USER"], DEFINES["YR_FLAG_BAD_ITEM"]
+OPT_ADAM, OPT_ADAMW = DEFINES["YR_OPT_ADAM"], DEFINES["YR_OPT_ADAMW"]
+PULL_USER_PHASE, PULL_ITEM_PHASE = DEFINES["YR_PULL_USER_PHASE"], DEFINES["YR_PULL_ITEM_PHASE"]
 SUPPORTED_WIDTHS = (16, 32, 64, 128)
 # BPR-MF alone also takes the wide widths: push-form training (csrc/bpr_mf.hip), the slab sweep of the fused
 # evaluation for k <= 16 (csrc/eval_topk.hip) and the score GEMM.  The pull form stays at SUPPORTED_WIDTHS.
@@ -151,11 +152,8 @@ def pull_supported(num_users, num_items, d):
 
 def bpr_mf_pull_workspace(max_batch, num_users, num_items, d, device):
     """Scratch buffer for :func:`bpr_mf_pull_step` (uint8 tensor, 256-byte aligned by torch)."""
-    lib = _lib.load()
-    n = lib.yr_bpr_mf_pull_workspace_bytes(int(max_batch), int(num_users), int(num_items), int(d))
-    if n < 0:
-        check(int(n), "yr_bpr_mf_pull_workspace_bytes")
-    return torch.empty(int(n), dtype=torch.uint8, device=device)
+    n = query_size("yr_bpr_mf_pull_workspace_bytes", max_batch, num_users, num_items, d)
+    return torch.empty(n, dtype=torch.uint8, device=device)
 
 
 PULL_RULE_FIELDS = ("split_min", "split_target", "row_min", "row_target", "row_quad", "row_max_parts",
@@ -173,9 +171,7 @@ def bpr_mf_pull_split_summary(batch, num_users, num_items, d, workspace=None):
     lib = _lib.load()
     rule = (ctypes.c_int32 * 8)()
     counters = (ctypes.c_int32 * 4)()
-    nb = int(lib.yr_bpr_mf_pull_item_buckets(int(num_items), int(d)))
-    if nb < 0:
-        check(nb, "yr_bpr_mf_pull_item_buckets")
+    nb = query_size("yr_bpr_mf_pull_item_buckets", num_items, d)
     parts = np.zeros(nb, np.int32)
     if workspace is None:
         rc = lib.yr_bpr_mf_pull_split_summary(None, 0, int(batch), int(d), int(num_users), int(num_items), None, None,
@@ -281,7 +277,7 @@ def spmm_csr(graph, X, out=None, accumulate=False, form=None):
     return out
 
 
-NGCF_MAX_LAYERS = 8
+NGCF_MAX_LAYERS = DEFINES["YR_NGCF_MAX_LAYERS"]
 
 
 def _ptr_array(tensors, what):
@@ -394,18 +390,12 @@ def ngcf_score(layers, num_users, user_id, pos_ids, neg_ids=None, err_flag=None)
 
 def ngcf_owned_score_workspace_bytes(n, B):
     """Bytes of scratch :func:`ngcf_score_backward` needs with ``deterministic=True`` (EngineError for refused sizes)."""
-    v = int(_lib.load().yr_ngcf_owned_score_workspace_bytes(int(n), int(B)))
-    if v < 0:
-        check(v, "yr_ngcf_owned_score_workspace_bytes")
-    return v
+    return query_size("yr_ngcf_owned_score_workspace_bytes", n, B)
 
 
 def ngcf_owned_dw_workspace_bytes(rows, d):
     """Bytes of scratch :func:`ngcf_dense_bwd` needs with ``deterministic=True`` over at most ``rows`` rows."""
-    v = int(_lib.load().yr_ngcf_owned_dw_workspace_bytes(int(rows), int(d)))
-    if v < 0:
-        check(v, "yr_ngcf_owned_dw_workspace_bytes")
-    return v
+    return query_size("yr_ngcf_owned_dw_workspace_bytes", rows, d)
 
 
 def _ngcf_scratch(workspace, nbytes, device, what):
@@ -521,7 +511,7 @@ def ngcf_dense_bwd(dEout, Eout, E, Z, W1, W2, dE, dW1, dW2, dZ=None, W1T=None, W
 
 
 ACT_IDENTITY, ACT_SIGMOID, ACT_RELU = 0, 1, 2
-COUNT_WORDS, COUNT_SLOTS = 2048, 64        # include/yelprec_engine.h YR_COUNT_WORDS / YR_COUNT_SLOTS
+COUNT_WORDS, COUNT_SLOTS = DEFINES["YR_COUNT_WORDS"], DEFINES["YR_COUNT_SLOTS"]
 
 
 def gemm_f32(A, B, transA=False, transB=False, out=None, bias=None, act=ACT_IDENTITY, accumulate=False,
@@ -697,10 +687,7 @@ CDAE_CATALOGUE_HIDDEN = (16, 32, 64, 128)      # the widths yr_cdae_catalogue_bc
 
 def cdae_catalogue_bce_workspace_floats(B, I, H):
     """Floats of the catalogue-BCE workspace (yr_cdae_catalogue_bce_workspace_floats)."""
-    n = _lib.load().yr_cdae_catalogue_bce_workspace_floats(int(B), int(I), int(H))
-    if n < 0:
-        check(int(n), "yr_cdae_catalogue_bce_workspace_floats")
-    return int(n)
+    return query_size("yr_cdae_catalogue_bce_workspace_floats", B, I, H)
 
 
 def cdae_catalogue_bce(z, Wo, bo, users, tgt_ptr, tgt_idx, act, grads=True, workspace=None, err_flag=None, out=None):
@@ -916,10 +903,7 @@ CDAE_OWNED_HIDDEN = (16, 32, 64, 128, 256, 512, 1024)
 
 def cdae_owned_workspace_bytes(B, I, H):
     """Bytes of the workspace yr_cdae_owned_decode and yr_cdae_owned_hidden_bwd share (yr_cdae_owned_workspace_bytes)."""
-    n = _lib.load().yr_cdae_owned_workspace_bytes(int(B), int(I), int(H))
-    if n < 0:
-        check(int(n), "yr_cdae_owned_workspace_bytes")
-    return int(n)
+    return query_size("yr_cdae_owned_workspace_bytes", B, I, H)
 
 
 def _owned_workspace(workspace, B, I, H, what):
@@ -1149,7 +1133,8 @@ def fused_eval_supports(k, d):
     return k <= 16 or (k <= 32 and d <= 64)
 
 
-EVAL_MODES = {"f32": 0, "bf16x3": 1}          # YR_EVAL_F32 / YR_EVAL_BF16X3 (include/yelprec_engine.h)
+EVAL_MODES = {"f32": DEFINES["YR_EVAL_F32"], "bf16x3": DEFINES["YR_EVAL_BF16X3"]}
+EVAL_FORMS = {None: 0, "two_roles": DEFINES["YR_EVAL_TWO_ROLES"], "four_waves": DEFINES["YR_EVAL_FOUR_WAVES"]}
 
 
 def mf_eval_topk(U, I, users, mask_ptr, mask_idx_sorted, k, mask_value=MASK_VALUE, out=None, sliced=True,
@@ -1174,23 +1159,21 @@ def mf_eval_topk(U, I, users, mask_ptr, mask_idx_sorted, k, mask_value=MASK_VALU
     if mask_idx_sorted is not None and mask_idx_sorted.numel() == 0:
         mask_ptr = mask_idx_sorted = None              # every list empty: an empty tensor has no address to pass
     mode = EVAL_MODES[precision]
-    planes_only = lib.yr_mf_eval_topk_planes_bytes(ni, d) if mode else 0
+    planes_only = query_size("yr_mf_eval_topk_planes_bytes", ni, d) if mode else 0
     if prescan is False or not sliced:
-        mode |= 2                                   # YR_EVAL_NO_PRESCAN
+        mode |= DEFINES["YR_EVAL_NO_PRESCAN"]
     elif prescan:
-        mode |= 4                                   # YR_EVAL_FORCE_PRESCAN
-    mode |= {None: 0, "two_roles": 8, "four_waves": 16}[form]   # YR_EVAL_TWO_ROLES / YR_EVAL_FOUR_WAVES
+        mode |= DEFINES["YR_EVAL_FORCE_PRESCAN"]
+    mode |= EVAL_FORMS[form]
     if out is None:
         out = torch.empty((n, k), dtype=torch.int64, device=U.device)
     if hint is not None and tuple(hint.shape) != (n, k):
         raise EngineError(f"hint must be [{n}, {k}] item ids, got {tuple(hint.shape)}")
     flag = new_error_flag(U.device)
     if sliced:
-        ws_bytes = lib.yr_mf_eval_topk_workspace_bytes(n, ni, d, int(k), mode)
+        ws_bytes = query_size("yr_mf_eval_topk_workspace_bytes", n, ni, d, k, mode)
     else:
         ws_bytes = planes_only + (-(-n * 4 // 256) * 256 if hint is not None else 0)
-    if ws_bytes < 0:
-        check(int(ws_bytes), "yr_mf_eval_topk_workspace_bytes")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=U.device) if ws_bytes else None
     check(lib.yr_mf_eval_topk_bias(_dev(U, torch.float32, "U"), _dev(I, torch.float32, "I"),
                               _opt(item_bias, torch.float32, "item_bias"),
@@ -1232,11 +1215,9 @@ def ngcf_eval_topk(layers, num_users, users, mask_ptr, mask_idx_sorted, k, mask_
         raise EngineError(f"hint must be [{n}, {k}] item ids, got {tuple(hint.shape)}")
     flag = new_error_flag(dev)
     if sliced:
-        ws_bytes = lib.yr_ngcf_eval_topk_workspace_bytes(n, ni, len(layers), d, int(k))
+        ws_bytes = query_size("yr_ngcf_eval_topk_workspace_bytes", n, ni, len(layers), d, k)
     else:
         ws_bytes = -(-n * 4 // 256) * 256 if hint is not None else 0
-    if ws_bytes < 0:
-        check(int(ws_bytes), "yr_ngcf_eval_topk_workspace_bytes")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     check(lib.yr_ngcf_eval_topk(ptrs, len(layers), d, _dev(users, torch.int64, "users"), n,
                                 int(num_users), ni, _opt(mask_ptr, torch.int64, "mask_ptr"),
@@ -1316,7 +1297,7 @@ def rank_metrics(topk, pos_ptr, pos_idx, pos_rows=None):
         raise EngineError("pos_ptr must have rows + 1 entries")
     if pos_rows is not None and pos_rows.numel() != n:
         raise EngineError("pos_rows must have one entry per row")
-    ws = torch.empty(lib.yr_rank_metrics_workspace_bytes(n) // 8, dtype=torch.float64, device=topk.device)
+    ws = torch.empty(query_size("yr_rank_metrics_workspace_bytes", n) // 8, dtype=torch.float64, device=topk.device)
     out = torch.empty(10, dtype=torch.float64, device=topk.device)
     idx = pos_idx if pos_idx.numel() else torch.zeros(1, dtype=torch.int64, device=topk.device)
     check(lib.yr_rank_metrics(_dev(topk, torch.int64, "topk"), n, k, _dev(pos_ptr, torch.int64, "pos_ptr"),
@@ -1327,12 +1308,12 @@ def rank_metrics(topk, pos_ptr, pos_idx, pos_rows=None):
 
 
 # ---- ranks of every held-out item against the catalogue (csrc/catalogue_rank.hip) and the metrics at any cutoff ----
-CATALOGUE_RANK_CAP = 16      # YR_CATALOGUE_RANK_CAP: targets per slot of the rank sweep
+CATALOGUE_RANK_CAP = DEFINES["YR_CATALOGUE_RANK_CAP"]     # targets per slot of the rank sweep
 SWEEP_TILE = 32              # csrc/s3rec_cb.h kSweepTile: rows (slots) per row tile, items per swept tile
 SWEEP_COL_CHUNK = 2048       # csrc/s3rec_cb.h kSweepColChunk: items per workgroup of the catalogue sweeps
 SWEEP_GRID_MAX = 2048        # csrc/s3rec_cb.h kSweepGridMax: workgroups per launch, the kernels loop from there
-METRICS_PER_K = 12           # YR_METRICS_PER_K
-METRICS_MAX_KS = 16          # YR_METRICS_MAX_KS
+METRICS_PER_K = DEFINES["YR_METRICS_PER_K"]
+METRICS_MAX_KS = DEFINES["YR_METRICS_MAX_KS"]
 
 
 def catalogue_rank_slots(pos_lengths):
@@ -1368,9 +1349,7 @@ def catalogue_ranks(layers_user, layers_item, users, pos_ptr, pos_idx, mask_ptr,
     if mask_idx_sorted is not None and mask_idx_sorted.numel() == 0:
         mask_ptr = mask_idx_sorted = None              # every list empty: an empty tensor has no address to pass
     dev = layers_user[0].device
-    ws_bytes = lib.yr_catalogue_ranks_workspace_bytes(n, nnz, ni, len(layers_user), d)
-    if ws_bytes < 0:
-        check(int(ws_bytes), "yr_catalogue_ranks_workspace_bytes")
+    ws_bytes = query_size("yr_catalogue_ranks_workspace_bytes", n, nnz, ni, len(layers_user), d)
     ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
     rank = out if out is not None else torch.empty(nnz, dtype=i64, device=dev)
     want_score = want_score or score_out is not None
@@ -1417,7 +1396,7 @@ def metrics_from_ranks(rank, pos_ptr, ks, num_items=None, mask_ptr=None):
     dev = pos_ptr.device
     if mask_ptr is not None and mask_ptr.numel() != n + 1:
         raise EngineError("metrics_from_ranks: mask_ptr must have rows + 1 entries")
-    ws = torch.empty(lib.yr_metrics_from_ranks_workspace_bytes(n, len(ks)) // 8, dtype=torch.float64, device=dev)
+    ws = torch.empty(query_size("yr_metrics_from_ranks_workspace_bytes", n, len(ks)) // 8, dtype=torch.float64, device=dev)
     out = torch.empty(len(ks) * METRICS_PER_K + 6, dtype=torch.float64, device=dev)
     kt = torch.tensor(ks, dtype=i64, device=dev)
     check(lib.yr_metrics_from_ranks(_dev(rank, i64, "rank") if rank.numel() else None, n, _dev(pos_ptr, i64, "pos_ptr"),
@@ -1475,7 +1454,7 @@ def adam_dense(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_de
                             1 if zero_grad else 0, _stream()), "yr_adam_dense")
 
 
-ADAM_MULTI_MAX = 16
+ADAM_MULTI_MAX = DEFINES["YR_ADAM_MULTI_MAX"]
 
 
 def adam_dense_flat(tensors, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, decoupled=False,
@@ -1551,7 +1530,7 @@ def dcn_assemble(U, I, C, S, attrs, user, item_a, item_b=None, attr_per_row=Fals
     return out
 
 
-DCN_OWNED_CHUNK = 256        # YR_DCN_OWNED_CHUNK: entries per chunk of an inverted attribute list
+DCN_OWNED_CHUNK = DEFINES["YR_DCN_OWNED_CHUNK"]        # entries per chunk of an inverted attribute list
 
 
 class DCNAttrLists:
@@ -1596,19 +1575,13 @@ def _list_ptr(keys, rows):
 
 def dcn_owned_head_workspace_bytes(units, F, H, L):
     """Bytes of scratch :func:`dcn_head` needs with ``deterministic=True`` and gradients (EngineError when refused)."""
-    v = int(_lib.load().yr_dcn_owned_head_workspace_bytes(int(units), int(F), int(H), int(L)))
-    if v < 0:
-        check(v, "yr_dcn_owned_head_workspace_bytes")
-    return v
+    return query_size("yr_dcn_owned_head_workspace_bytes", units, F, H, L)
 
 
 def dcn_owned_scatter_workspace_bytes(num_users, num_items, B, D, lists):
     """Bytes of scratch :func:`dcn_assemble_bwd` needs with ``deterministic=True`` for a batch of B triplets."""
-    v = int(_lib.load().yr_dcn_owned_scatter_workspace_bytes(int(num_users), int(num_items), int(B), int(D),
-                                                             lists.cat_chunks, lists.sc_chunks))
-    if v < 0:
-        check(v, "yr_dcn_owned_scatter_workspace_bytes")
-    return v
+    return query_size("yr_dcn_owned_scatter_workspace_bytes", num_users, num_items, B, D, lists.cat_chunks,
+                      lists.sc_chunks)
 
 
 def dcn_assemble_bwd(dx, attrs, user, item_a, item_b, gU, gI, gC, gS, num_users, attr_per_row=False, err_flag=None,
@@ -1807,10 +1780,7 @@ _S3REC_WS_ARRAYS = (("h_in", 1, 0), ("qkv", 0, 3), ("A", 0, 1), ("x1", 1, 0), ("
 
 def s3rec_train_workspace_floats(B, L, E, heads, blocks):
     """Floats of the training workspace (yr_s3rec_train_workspace_floats)."""
-    n = _lib.load().yr_s3rec_train_workspace_floats(B, L, E, heads, blocks)
-    if n < 0:
-        check(int(n), "yr_s3rec_train_workspace_floats")
-    return int(n)
+    return query_size("yr_s3rec_train_workspace_floats", B, L, E, heads, blocks)
 
 
 def s3rec_workspace_views(ws, B, L, E, heads, blocks):
@@ -2012,10 +1982,7 @@ def s3rec_item_grad_one(X, d_emb, d_item, err_flag=None):
 
 def s3rec_catalogue_bce_workspace_floats(N, R, E):
     """Floats of the catalogue-BCE workspace (yr_s3rec_catalogue_bce_workspace_floats)."""
-    n = _lib.load().yr_s3rec_catalogue_bce_workspace_floats(N, R, E)
-    if n < 0:
-        check(int(n), "yr_s3rec_catalogue_bce_workspace_floats")
-    return int(n)
+    return query_size("yr_s3rec_catalogue_bce_workspace_floats", N, R, E)
 
 
 def s3rec_catalogue_bce(F, T, zscale, yscale, key, tgt_ptr=None, tgt_idx=None, grads=True, want_dF=None, want_dT=None,
@@ -2058,10 +2025,7 @@ def s3rec_catalogue_bce(F, T, zscale, yscale, key, tgt_ptr=None, tgt_idx=None, g
 # ---- S3Rec full-catalogue evaluation (csrc/s3rec_rank.hip: the catalogue rank) ----
 def s3rec_catalogue_rank_workspace_bytes(N, R, E):
     """Bytes of the catalogue-rank workspace (yr_s3rec_catalogue_rank_workspace_bytes)."""
-    n = _lib.load().yr_s3rec_catalogue_rank_workspace_bytes(N, R, E)
-    if n < 0:
-        check(int(n), "yr_s3rec_catalogue_rank_workspace_bytes")
-    return int(n)
+    return query_size("yr_s3rec_catalogue_rank_workspace_bytes", N, R, E)
 
 
 def s3rec_catalogue_rank(H, T, target, excl_ptr=None, excl_idx=None, excl_rows=None, first_col=1, want_score=False,
@@ -2096,7 +2060,7 @@ def s3rec_catalogue_rank(H, T, target, excl_ptr=None, excl_idx=None, excl_rows=N
     return (rank, score) if want_score else rank
 
 
-S3REC_MODES = {"train": 0, "valid": 1, "test": 2}          # YR_S3REC_TRAIN / VALID / TEST
+S3REC_MODES = {"train": DEFINES["YR_S3REC_TRAIN"], "valid": DEFINES["YR_S3REC_VALID"], "test": DEFINES["YR_S3REC_TEST"]}
 S3REC_MAX_NEG = 128
 
 

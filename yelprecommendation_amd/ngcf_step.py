@@ -80,11 +80,8 @@ class NGCFStep:
 
     def _workspace(self, B):
         if self._ws is None or B > self._ws_batch:
-            size = (self._lib.yr_ngcf_step_ordered_workspace_bytes if self.deterministic
-                    else self._lib.yr_ngcf_step_workspace_bytes)
-            nbytes = int(size(self.n, self.D, self.K, B))
-            if nbytes < 0:
-                engine.check(nbytes, "yr_ngcf_step_workspace_bytes")
+            size = "yr_ngcf_step_ordered_workspace_bytes" if self.deterministic else "yr_ngcf_step_workspace_bytes"
+            nbytes = engine.query_size(size, self.n, self.D, self.K, B)
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.params[0].device)
             self._ws_batch = B
         return self._ws
